@@ -13,10 +13,17 @@ rank inflates its piece (pieces after the first in piece mode), and the decoded 
 where they were decoded (shard.scatter_inflate, gather=False).  value = total uncompressed
 bytes of all ranks / max-over-ranks step time.
 
-  python bench.py                          # N=1, defaults (+ the per-config sub-records)
+  python bench.py --gpus 1 --steps K --warmup W   # the headline figure only
+  python bench.py --full                           # + everything listed below
+  python bench.py --dump-outputs DIR               # + what the last timed step computed, as .npy
   torchrun --nproc-per-node N bench.py --gpus N [--strong]
 
-Prints ONE JSON line on rank 0.  Besides the contract fields it carries, at N = 1:
+Prints ONE JSON line on rank 0.  A plain run loads the corpus, warms up, times the steps and
+prints the line (metric, value, ms_per_step, the per-direction and per-kernel times of the timed
+steps themselves, and roundtrip_ok of the last timed step's output).  --dump-outputs DIR writes,
+after the timed steps, the arrays a caller of the timed path receives from its last step (see
+dump_outputs).  With --full the round trip is also verified in a step of its own before the
+timed region, the device-to-device copy ceiling is measured, and at N = 1 the line carries:
   corpora      the same round trip on the other Appendix-B corpora (1 GiB each): GB/s per
                direction, ratio next to the reference's level-2 ratio and zlib-1's, the
                roofline fraction of each direction's kernels
@@ -105,7 +112,16 @@ def parse():
     p.add_argument("--no-extras", action="store_true", help="skip the per-config sub-records")
     p.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
     p.add_argument("--sub", type=int, default=4, help="N > 1: sub-shards per rank in the pipelined gather")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the pre-timing verification step, "
+                        "the d2d copy ceiling, the per-config sub-records and the CPU baseline "
+                        "(--no-extras / --no-cpu-baseline drop the last two again)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def cpu_model():
@@ -458,6 +474,40 @@ def foreign_record(torch, ctx, dev, stream, kind="text", nbytes=GiB, pieces=8):
             "vs_reference_1core": round(nbytes / (med * 1e-3) / 1e6 / ref, 1) if ref else None}
 
 
+DUMP_SEED = 20240607
+DUMP_SAMPLE = 4 << 20   # elements of each sampled array (float32: 16 MiB per array)
+DUMP_BLOCK = 65536      # bytes per entry of the *_block_sums arrays
+
+
+def dump_outputs(out_dir, torch, arrays):
+    """--dump-outputs: for every (name, 1-D uint8 device tensor) of what the last timed step
+    handed its caller, write under out_dir
+      <name>_len.npy         float64 [1]: its length in bytes
+      <name>_block_sums.npy  float64: the byte sum of every DUMP_BLOCK bytes of the whole array
+                             (exact in float64), so every byte of the array bears on the dump
+      <name>_sample.npy      float32: the whole array where it has at most DUMP_SAMPLE bytes,
+                             otherwise its bytes at DUMP_SAMPLE sorted positions drawn by a
+                             generator seeded with DUMP_SEED (the same positions whenever the
+                             length is the same)
+    About 32 MiB in all for the two arrays of a round trip."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        m = t.numel()
+        np.save(os.path.join(out_dir, f"{name}_len.npy"), np.array([m], dtype=np.float64))
+        whole = m // DUMP_BLOCK * DUMP_BLOCK
+        sums = t[:whole].view(whole // DUMP_BLOCK, DUMP_BLOCK).sum(dim=1, dtype=torch.int64)
+        if m > whole:
+            sums = torch.cat([sums, t[whole:m].sum(dtype=torch.int64).reshape(1)])
+        np.save(os.path.join(out_dir, f"{name}_block_sums.npy"), sums.cpu().numpy().astype(np.float64))
+        if m <= DUMP_SAMPLE:
+            sample = t[:m]
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, m, size=DUMP_SAMPLE, dtype=np.int64))
+            sample = t[:m].index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, f"{name}_sample.npy"), sample.cpu().numpy().astype(np.float32))
+
+
 def main():
     a = parse()
     import torch
@@ -487,15 +537,22 @@ def main():
     if world == 1:
         for _ in range(a.warmup):
             run.step(a.level)
-        # correctness of the round trip (outside the timed region)
-        _, clen, olen, _, _ = run.step(a.level)
-        ok = run.verify(olen)
+        ok = True
+        if a.full:
+            # correctness of the round trip in a step of its own (outside the timed region)
+            _, clen, olen, _, _ = run.step(a.level)
+            ok = run.verify(olen)
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         for _ in range(a.steps):
             recs.append(run.step(a.level))
         torch.cuda.synchronize(dev)
         elapsed = time.perf_counter() - t0
+        # the last timed step's own output against its input (after the timed region)
+        ok = ok and run.verify(recs[-1][2])
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, torch, {"compressed": run.d_comp[: recs[-1][1]],
+                                                 "decoded": run.d_out[: recs[-1][2]]})
     else:
         # the whole stream lands on rank 0; every rank's decoded piece is sized by the cuts
         gathered = torch.empty(world * run.bound + 64, dtype=torch.uint8, device=dev) if rank == 0 else None
@@ -518,6 +575,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         split_ok = all(r[3] for r in dist_recs)
+        if a.dump_outputs and rank == 0:  # rank 0's view: the gathered stream and its decoded piece
+            dump_outputs(a.dump_outputs, torch, {"compressed": gathered[: dist_recs[-1][1]],
+                                                 "decoded": run.d_out[: dist_recs[-1][2]]})
         t_dg = sum(r[0][0].elapsed_time(r[0][1]) for r in dist_recs) / len(dist_recs)
         t_si = sum(r[0][1].elapsed_time(r[0][2]) for r in dist_recs) / len(dist_recs)
         # kernel times and the roofline: this rank's shard as one local round trip, after the
@@ -531,14 +591,14 @@ def main():
     # practical HBM ceiling: a device-to-device copy of the shard, after the timed
     # region, on torch's current stream where its events are recorded; bytes = N read + N written
     copy_ms = 1e9
-    for _ in range(3):
+    for _ in range(3 if a.full else 0):
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         c0.record()
         run.d_out[:n].copy_(run.d_in[:n])
         c1.record()
         c1.synchronize()
         copy_ms = min(copy_ms, c0.elapsed_time(c1))
-    d2d_gbps = 2 * n / (copy_ms * 1e-3) / 1e9
+    d2d_gbps = 2 * n / (copy_ms * 1e-3) / 1e9 if a.full else None
 
     ms_step = elapsed / a.steps * 1e3
     s = summarize(recs, n)
@@ -594,7 +654,7 @@ def main():
                          "traffic": traffic, "kernel": dom,
                          "alg_bytes_per_launch": s["alg"],
                          "frac_deflate": round(s["frac_def"], 5), "frac_inflate": round(s["frac_inf"], 5),
-                         "d2d_copy_GBps": round(d2d_gbps, 1)},
+                         "d2d_copy_GBps": round(d2d_gbps, 1) if a.full else None},
             "cpu_baseline": None,
         }
         if world > 1:
@@ -608,7 +668,7 @@ def main():
                                         "behind it (RCCL P2P), proven cuts, piece-mode inflate on every rank; "
                                         "decoded bytes stay on the rank that decoded them; kernel_ms / roofline "
                                         "from a local round trip of rank 0's shard after the timed region"}})
-    if world == 1 and not a.no_extras:
+    if a.full and world == 1 and not a.no_extras:
         # sub-records (outside the timed region): the other corpora, C3 and C5
         extras = {}
         for kind in ("text", "mixed", "random", "zeros", "bmp"):
@@ -622,7 +682,7 @@ def main():
         res["c4_64k"] = c4_record(run, dev, a.level, 3)
         res["foreign_1GiB"] = foreign_record(torch, ctx, dev, stream)
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(a.corpus, min(a.cpu_sample, n), a.level, a.cpu_slice)
             except Exception as e:  # the baseline is informative, never fatal

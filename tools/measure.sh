@@ -1,8 +1,10 @@
 set -e
-mkdir -p gpurun_out && cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rm -rf gpurun_out/prof gpurun_out/pmcF gpurun_out/pmcW  # (also clear them locally before merging)
-timeout -k 10 400 python bench.py > gpurun_out/bench_repeat.json 2> gpurun_out/bench_repeat.err
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/bench_prof.json 2> gpurun_out/bench_prof.err
-timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmcF --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > gpurun_out/pmcF.json 2> gpurun_out/pmcF.err
-timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmcW --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > gpurun_out/pmcW.json 2> gpurun_out/pmcW.err
-timeout -k 10 400 python bench.py --corpus text > gpurun_out/bench_text.json 2> gpurun_out/bench_text.err
+# run from the repository root; results go to $OUT (default build/measure, which git ignores)
+OUT=${OUT:-build/measure}
+mkdir -p "$OUT" && export TMPDIR=/tmp
+rm -rf "$OUT"/prof "$OUT"/pmcF "$OUT"/pmcW  # (also clear them locally before merging)
+timeout -k 10 600 python bench.py --full > "$OUT"/bench_repeat.json 2> "$OUT"/bench_repeat.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT"/prof --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT"/bench_prof.json 2> "$OUT"/bench_prof.err
+timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d "$OUT"/pmcF --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > "$OUT"/pmcF.json 2> "$OUT"/pmcF.err
+timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d "$OUT"/pmcW --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > "$OUT"/pmcW.json 2> "$OUT"/pmcW.err
+timeout -k 10 600 python bench.py --full --corpus text > "$OUT"/bench_text.json 2> "$OUT"/bench_text.err
