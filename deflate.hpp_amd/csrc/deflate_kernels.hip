@@ -451,14 +451,54 @@ struct DfSmem {
 // dead -- after its token words are written -- so its memory latency passes during the stores
 // and the loop's bookkeeping.  The loop's closing
 // __syncthreads waits for it (an LDS-DMA load counts on vmcnt).
-template <int SEG>
+// Where segment `seg` of SEG bytes lies.  One stream (BATCH false): computed from A.in / A.n.
+// A batch: read from the segment table (A.btab), whose entries span several buffers.
+struct DfSegAddr {
+    const uint8_t* src;  // the segment's first byte
+    uint64_t tail;       // bytes readable from src (to the end of the segment's own buffer)
+    uint32_t nb;         // the segment's bytes (<= SEG)
+    bool is_last;        // the last segment of its stream (BFINAL when the stream is final)
+};
+template <int SEG, bool BATCH>
+__device__ __forceinline__ DfSegAddr df_seg_addr(const DeflateArgs& A, uint64_t seg) {
+    DfSegAddr s;
+    if constexpr (BATCH) {
+        const DeflateBatchSeg e = A.btab[seg];
+        s.src = e.src;
+        s.tail = e.tail;
+        s.nb = e.nb;
+        s.is_last = (e.buf & DF_BATCH_LAST) != 0;
+    } else {
+        const uint64_t base = seg * (uint64_t)SEG;
+        s.src = A.in + base;
+        s.tail = A.n - base;
+        s.nb = (uint32_t)min((uint64_t)SEG, A.n - base);
+        s.is_last = seg + 1 == A.nseg;
+    }
+    return s;
+}
+
+template <int SEG, bool BATCH>
 __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t seg, DfSmem<SEG>& S) {
-    const uint64_t nbase = (seg + gridDim.x) * (uint64_t)SEG;
-    const bool go = seg + gridDim.x < A.nseg && nbase + SEG <= A.n &&
-                    ((reinterpret_cast<uintptr_t>(A.in + nbase) & 15) == 0);
+    bool go;
+    const uint8_t* nsrc;
+    if constexpr (BATCH) {
+        go = seg + gridDim.x < A.nseg;
+        if (go) {
+            const DeflateBatchSeg e = A.btab[seg + gridDim.x];
+            nsrc = e.src;
+            go = e.nb == (uint32_t)SEG && ((reinterpret_cast<uintptr_t>(nsrc) & 15) == 0);
+        } else {
+            nsrc = nullptr;
+        }
+    } else {
+        const uint64_t nbase = (seg + gridDim.x) * (uint64_t)SEG;
+        nsrc = A.in + nbase;
+        go = seg + gridDim.x < A.nseg && nbase + SEG <= A.n && ((reinterpret_cast<uintptr_t>(A.in + nbase) & 15) == 0);
+    }
     if (go) {
         const int t = df_tid();
-        const uint4* src = reinterpret_cast<const uint4*>(A.in + nbase) + t;
+        const uint4* src = reinterpret_cast<const uint4*>(nsrc) + t;
         // one wave-instruction writes 64 x 16 B contiguously from a wave-uniform LDS base
         uint4* dst = reinterpret_cast<uint4*>(S.data32) + (t & ~63);
 #pragma unroll
@@ -486,22 +526,22 @@ __device__ __forceinline__ uint32_t next_tok(const uint32_t* tokmap, uint32_t& w
 
 // L3: level 3 (chain search, lazy parse) -- a separate instantiation, so the level-2 kernel
 // carries none of that code (the 1024-thread kernel's register allocation and code size)
-template <int SEG, bool L3>
+template <int SEG, bool L3, bool BATCH>
 __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG>& S, uint64_t seg,
                                                 bool& staged) {
     [[maybe_unused]] constexpr int NWALK = DfSmem<SEG>::NWALK;
     constexpr int HT = DfSmem<SEG>::HT;
     constexpr int NMAP = SEG / 32;
     const int t = df_tid();
-    const uint64_t base = seg * (uint64_t)SEG;
-    const uint32_t nb = (uint32_t)min((uint64_t)SEG, A.n - base);
+    const DfSegAddr sa = df_seg_addr<SEG, BATCH>(A, seg);
+    const uint32_t nb = sa.nb;
     constexpr int level = L3 ? 3 : 2;  // (the front kernel runs at levels 2 and 3 only)
     uint8_t* const dbytes = reinterpret_cast<uint8_t*>(S.data32);
     DMX_PHASE(A.dbg, seg, 0);
 
     // ---- load the segment into LDS (16 B per lane when aligned) ------------------------
     {
-        const uint8_t* src = A.in + base;
+        const uint8_t* src = sa.src;
         const uint32_t nvec = nb / 16;
         if (staged) {  // loaded during the previous segment (df_prefetch_next)
         } else if ((((uintptr_t)src) & 15) == 0) {
@@ -1188,7 +1228,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         __syncthreads();  // every read of the segment's bytes is done
         if (DMX_DF_HIST && t < (int)kDeflateHistWords)
             A.tok[seg * (uint64_t)A.tok_stride + A.tok_stride - kDeflateHistWords + t] = S.hist[2 * t] | (S.hist[2 * t + 1] << 16);
-        staged = df_prefetch_next<SEG>(A, seg, S);
+        staged = df_prefetch_next<SEG, BATCH>(A, seg, S);
         DMX_PHASE(A.dbg, seg, 10);
     }
 }
@@ -1198,23 +1238,25 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
 // registers per lane, which amdgpu_waves_per_eu(8) asks for.
 // Persistent workgroups (as many as fit the GPU at once): workgroup b compresses segments
 // b, b + G, b + 2G, ... and loads each next segment while it works on the current one.
-template <int SEG, bool L3>
+template <int SEG, bool L3, bool BATCH>
 __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SEG>& S) {
     bool staged = false;  // S.data32 already holds the segment's bytes
     for (uint64_t seg = blockIdx.x; seg < A.nseg; seg += gridDim.x) {
-        deflate_segment<SEG, L3>(A, S, seg, staged);
+        deflate_segment<SEG, L3, BATCH>(A, S, seg, staged);
         __syncthreads();  // the next segment reuses the LDS (and its prefetch has landed)
     }
 }
-template <int SEG, bool L3>
+// BATCH: the segments come from the batch's segment table (df_seg_addr); the default
+// instantiations are the single-stream kernels
+template <int SEG, bool L3, bool BATCH = false>
 __global__ __launch_bounds__(DF_NT) void k_deflate_segments(DeflateArgs A) {
     __shared__ DfSmem<SEG> S;
-    deflate_segments<SEG, L3>(A, S);
+    deflate_segments<SEG, L3, BATCH>(A, S);
 }
-template <bool L3>
+template <bool L3, bool BATCH = false>
 __global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_deflate_segments16(DeflateArgs A) {
     __shared__ DfSmem<16384> S;
-    deflate_segments<16384, L3>(A, S);
+    deflate_segments<16384, L3, BATCH>(A, S);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1529,13 +1571,13 @@ struct EmSrc {
         return (v >> 31) ? 0u : (v >> 24) & 3u;
     }
 };
+// inb: the part's first input byte, tail: the bytes readable from it (to the end of its buffer)
 template <bool RAW>
-__device__ EmSrc em_src(const DeflateArgs& A, uint64_t fseg, uint64_t base, uint32_t nb) {
+__device__ EmSrc em_src(const DeflateArgs& A, uint64_t fseg, const uint8_t* inb, uint64_t tail, uint32_t nb) {
     EmSrc s;
-    const uint8_t* const inb = A.in + base;
     s.mis = (uint32_t)(reinterpret_cast<uintptr_t>(inb) & 3);
     s.inw = reinterpret_cast<const uint32_t*>(inb - s.mis);
-    s.in_words_end = (A.n - base + s.mis + 3) / 4;
+    s.in_words_end = (tail + s.mis + 3) / 4;
     s.nb = nb;
     s.raw = RAW || A.ntok[fseg] == EM_ALL_LITERALS;
     s.ntok = s.raw ? (nb + 3) / 4 : A.ntok[fseg];
@@ -1555,18 +1597,21 @@ __device__ __forceinline__ uint32_t em_stored_hdr(uint32_t q, bool fin, uint32_t
 // front segments 2s and 2s + 1), and this wave codes both halves' token words as ONE block --
 // one histogram, one code, one header -- so the block is a 64 KiB DEFLATE block whose second
 // half simply never refers into the first (valid: a reference may, but need not, reach back).
-template <int SEG, bool RAW>
+template <int SEG, bool RAW, bool BATCH>
 __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
+    static_assert(!BATCH || SEG <= 32768, "a batch does not pair front segments into 64 KiB blocks");
     constexpr uint32_t NH = SEG > 32768 ? 2u : 1u;  // front segments per block
     constexpr uint32_t HB = (uint32_t)SEG / NH;
     const int lane = lane_id();
     EM_PHASE(A.dbg, seg, 4);
-    const uint64_t base = seg * (uint64_t)SEG;
-    const uint32_t nb = (uint32_t)min((uint64_t)SEG, A.n - base);
+    const DfSegAddr sa = df_seg_addr<SEG, BATCH>(A, seg);
+    const uint32_t nb = sa.nb;
     const uint32_t np = (nb + HB - 1) / HB;  // parts of this block (the last block may be short)
-    const bool is_final = (seg + 1 == A.nseg) && A.final_last;
+    const bool is_final = sa.is_last && A.final_last;
     uint32_t* const slot = reinterpret_cast<uint32_t*>(A.slots + seg * (uint64_t)A.slot_bytes);
-    auto part = [&](uint32_t h) { return em_src<RAW>(A, seg * NH + h, base + (uint64_t)h * HB, min(HB, nb - h * HB)); };
+    auto part = [&](uint32_t h) {
+        return em_src<RAW>(A, seg * NH + h, sa.src + (uint64_t)h * HB, sa.tail - (uint64_t)h * HB, min(HB, nb - h * HB));
+    };
     // a stored form longer than 65535 bytes (LEN is 16 bits) is two stored blocks of 32 KiB
     const uint32_t nsto = nb > 65535u ? 2u : 1u;
     const uint32_t n1 = nsto == 2 ? 32768u : nb;
@@ -1787,10 +1832,10 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
     // ---- stored: [BFINAL|00][LEN][NLEN][data] (two such blocks above 65535 bytes), then the
     // empty stored block unless final ------------------------------------------------------
     const uint32_t total = (uint32_t)stored_bytes;
-    const uint8_t* const inb = A.in + base;
+    const uint8_t* const inb = sa.src;
     const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(inb) & 3);
     const uint32_t* const inw = reinterpret_cast<const uint32_t*>(inb - mis);
-    const uint64_t in_words_end = (A.n - base + mis + 3) / 4;  // readable words from inw
+    const uint64_t in_words_end = (sa.tail + mis + 3) / 4;  // readable words from inw
     const uint32_t d2 = 10 + n1;  // first output byte of the second block's data (nsto == 2)
     // 16 output bytes per lane and step, four steps in flight (the copy is latency-bound):
     // output bytes [16 k, 16 k + 16) inside a block's data are input bytes shifted by that
@@ -1848,7 +1893,7 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
 }
 
 // RAW: level 1 (the input's bytes are the tokens) and level 0; else the front kernel's words
-template <int SEG, bool RAW>
+template <int SEG, bool RAW, bool BATCH = false>
 __global__ __launch_bounds__(64 * EM_NW)
 #if DMX_EM_OCC
 __attribute__((amdgpu_waves_per_eu(DMX_EM_OCC)))
@@ -1857,7 +1902,7 @@ void k_deflate_emit(DeflateArgs A) {
     __shared__ EmWave Ws[EM_NW];
     const uint64_t seg = (uint64_t)blockIdx.x * EM_NW + (threadIdx.x >> 6);
     if (seg >= A.nseg) return;
-    em_segment<SEG, RAW>(A, Ws[threadIdx.x >> 6], seg);
+    em_segment<SEG, RAW, BATCH>(A, Ws[threadIdx.x >> 6], seg);
 }
 
 // exclusive scan of segment sizes -> offsets (single workgroup of 1024 threads).  Thread t owns
@@ -1964,17 +2009,8 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_apply(const uint32_t* v, uint6
 // copy each segment slot to its place in the contiguous stream
 // one wave per segment, four per workgroup (a workgroup per segment was dispatch-bound on
 // small segments: 32768 workgroups for ~480 B each on the repeat corpus)
-__global__ __launch_bounds__(256) void k_compact(const uint8_t* slots, uint32_t slot_bytes,
-                                                  const uint32_t* sizes, const uint64_t* offs,
-                                                  uint64_t nseg, uint8_t* out, uint64_t cap) {
-    const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63;
-    if (s >= nseg) return;
-    const uint32_t sz = sizes[s];
-    const uint64_t o = offs[s];
-    const uint8_t* src = slots + s * (uint64_t)slot_bytes;
-    if (o + sz > cap) return;
-    uint8_t* dst = out + o;
+// one wave moves the sz bytes of a slot (256-B aligned) to dst
+__device__ __forceinline__ void compact_copy(const uint8_t* src, uint8_t* dst, uint32_t sz, uint32_t lane) {
     // align the destination to 4 bytes, then move words built with alignbyte
     const uint32_t head = (uint32_t)((4 - ((uintptr_t)dst & 3)) & 3);
     const uint32_t hb = min(head, sz);
@@ -1990,6 +2026,55 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* slots, uint32_t 
     }
     for (uint32_t i = hb + nw * 4 + lane; i < sz; i += 64) dst[i] = src[i];
 }
+__global__ __launch_bounds__(256) void k_compact(const uint8_t* slots, uint32_t slot_bytes,
+                                                  const uint32_t* sizes, const uint64_t* offs,
+                                                  uint64_t nseg, uint8_t* out, uint64_t cap) {
+    const uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (s >= nseg) return;
+    const uint32_t sz = sizes[s];
+    const uint64_t o = offs[s];
+    const uint8_t* src = slots + s * (uint64_t)slot_bytes;
+    if (o + sz > cap) return;
+    compact_copy(src, out + o, sz, lane);
+}
+
+// k_compact for a batch.  Waves [0, nseg): segment s goes to its buffer's output at the scanned
+// offset less the offset of the buffer's first segment, when it ends within the buffer's
+// capacity.  The waves after them: one lane per buffer writes its result -- the stream length
+// (the span of its segments' offsets; A.total holds the end of the last one), DMX_ERR_CAPACITY
+// when that exceeds the capacity -- and, for a buffer without segments (an empty input), the
+// empty final fixed-Huffman block 03 00 that the single-buffer call writes.
+__global__ __launch_bounds__(256) void k_compact_batch(DeflateArgs A) {
+    const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (w < A.nseg) {
+        const uint32_t b = A.btab[w].buf & ~DF_BATCH_LAST;
+        const uint32_t sz = A.sizes[w];
+        const uint64_t rel = A.offsets[w] - A.offsets[A.bfirst[b]];
+        if (rel + sz > A.bcap[b]) return;
+        compact_copy(A.slots + w * (uint64_t)A.slot_bytes, A.bout[b] + rel, sz, lane);
+        return;
+    }
+    const uint64_t b = (w - A.nseg) * 64 + lane;
+    if (b >= A.nbuf) return;
+    const uint64_t s0 = A.bfirst[b], s1 = A.bfirst[b + 1];
+    uint64_t bytes;
+    if (s0 == s1) {
+        bytes = 2;
+        if (A.bcap[b] >= 2) {
+            A.bout[b][0] = 0x03;
+            A.bout[b][1] = 0x00;
+        }
+    } else {
+        bytes = (s1 < A.nseg ? A.offsets[s1] : *A.total) - A.offsets[s0];
+    }
+    ::dmx_batch_result r;
+    r.bytes = bytes;
+    r.status = bytes > A.bcap[b] ? DMX_ERR_CAPACITY : DMX_OK;
+    r.path = 0;
+    A.bres[b] = r;
+}
 
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st,
                           hipEvent_t ev_main0, hipEvent_t ev_main1) {
@@ -2004,6 +2089,30 @@ hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t 
     const uint64_t fit = (uint64_t)max(ncu, 1) * (uint64_t)max(per, 1);
     const uint32_t grid = (uint32_t)std::min<uint64_t>(A.nseg, fit);  // host min(int, int) would truncate
     if (ev_main0) (void)hipEventRecord(ev_main0, st);
+    if (A.btab) {  // a batch: the same stages over the segment table, k_compact_batch at the end
+        if (seg_bytes != 32768 && seg_bytes != 16384) return hipErrorInvalidValue;
+        const bool l3 = A.level >= 3, s32 = seg_bytes == 32768;
+        if (grid && A.level >= 2) {
+            if (s32 && l3) hipLaunchKernelGGL((k_deflate_segments<32768, true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+            else if (s32) hipLaunchKernelGGL((k_deflate_segments<32768, false, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+            else if (l3) hipLaunchKernelGGL((k_deflate_segments16<true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+            else hipLaunchKernelGGL((k_deflate_segments16<false, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+        }
+        if (A.nseg) {
+            const uint32_t eg = (uint32_t)((A.nseg + EM_NW - 1) / EM_NW);
+            const bool raw = A.level < 2;
+            if (s32 && raw) hipLaunchKernelGGL((k_deflate_emit<32768, true, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
+            else if (s32) hipLaunchKernelGGL((k_deflate_emit<32768, false, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
+            else if (raw) hipLaunchKernelGGL((k_deflate_emit<16384, true, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
+            else hipLaunchKernelGGL((k_deflate_emit<16384, false, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
+        }
+        if (ev_main1) (void)hipEventRecord(ev_main1, st);
+        const hipError_t e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st);
+        if (e != hipSuccess) return e;
+        const uint64_t waves = A.nseg + (A.nbuf + 63) / 64;
+        hipLaunchKernelGGL(k_compact_batch, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, st, A);
+        return hipGetLastError();
+    }
     if (grid && A.level >= 2) {  // match finding + parse -> token words (levels 0-1 have none)
         const bool l3 = A.level >= 3;
         if (seg_bytes == 65536) {  // 64 KiB blocks: the front kernel matches their 32 KiB halves

@@ -88,6 +88,7 @@ struct dmx_ctx {
     DevBuf fbreg, fbJ, fbvis;  // fixed-code regions: {E, T, first super block} + super-block regions, jumps, visits
     DevBuf fbJraw, fbJsub, fbcbit, fbucb;  // regions: chunk maps, sub-chunk entries, chunk entries, unit chunk
     DevBuf ck;  // checksum scratch (checksum.hip) + the 4-byte result at its start
+    DevBuf btab, bres;  // batch calls: the uploaded tables / descriptors; the results + the ticket
     bool timing = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_df = nullptr;          // end of the last deflate's work (its scratch is reused)
@@ -1274,6 +1275,167 @@ int inflate_device_async_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8
     return DMX_OK;
 }
 
+// ---- batched calls (dmx_deflate_batch_device / dmx_inflate_batch_device) ----------------------
+
+// Batch deflate: one segment table over all buffers (DESIGN "Batched API"), uploaded with the
+// per-buffer arrays in one copy; one front launch, one emit launch, one scan and k_compact_batch
+// cover the batch, and the results come back in the call's only host synchronisation.
+int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count, int level,
+                         uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, hipStream_t st) {
+    if (level < 0 || level > 3) level = 1;  // as deflate_device_locked
+    const uint32_t seg = c->seg;
+    uint64_t nseg = 0;
+    for (size_t i = 0; i < count; i++) {
+        if ((!d_in[i] && n[i]) || (!d_out[i] && cap[i])) return DMX_ERR_ARG;
+        nseg += (n[i] + seg - 1) / seg;
+    }
+    // host image of the upload: segment table | first segment of each buffer | outputs | capacities
+    const size_t off_first = nseg * sizeof(DeflateBatchSeg);
+    const size_t off_out = off_first + (count + 1) * 8, off_cap = off_out + count * 8, bytes = off_cap + count * 8;
+    std::vector<uint64_t> image;
+    try {
+        image.resize(bytes / 8);
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    static_assert(sizeof(DeflateBatchSeg) == 24 && sizeof(void*) == 8, "the upload image is built from 8-byte words");
+    uint8_t* const img = reinterpret_cast<uint8_t*>(image.data());
+    DeflateBatchSeg* tab = reinterpret_cast<DeflateBatchSeg*>(img);
+    uint64_t* first = reinterpret_cast<uint64_t*>(img + off_first);
+    uint64_t s = 0;
+    for (size_t i = 0; i < count; i++) {
+        first[i] = s;
+        for (size_t o = 0; o < n[i]; o += seg, s++) {
+            const size_t rest = n[i] - o;
+            tab[s].src = d_in[i] + o;
+            tab[s].tail = rest;
+            tab[s].nb = (uint32_t)std::min<size_t>(seg, rest);
+            tab[s].buf = (uint32_t)i | (rest <= seg ? DF_BATCH_LAST : 0u);
+        }
+        reinterpret_cast<uint64_t*>(img + off_out)[i] = (uint64_t)(uintptr_t)d_out[i];
+        reinterpret_cast<uint64_t*>(img + off_cap)[i] = cap[i];
+    }
+    first[count] = s;
+
+    if (c->df_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_df, 0));
+    begin_timing(c, st);
+    const uint32_t slot_bytes = seg + 256;
+    const uint32_t tok_stride = level >= 2 ? deflate_tok_stride(seg) : 0u;
+    if (!c->btab.ensure(bytes) || !c->bres.ensure(count * sizeof(dmx_batch_result)) ||
+        !c->slots.ensure(std::max<uint64_t>(1, nseg) * (size_t)slot_bytes) || !c->sizes.ensure(std::max<uint64_t>(1, nseg) * 4) ||
+        !c->offs.ensure(scan_words(nseg) * 8) ||
+        !c->dtok.ensure(std::max<uint64_t>(1, nseg * (uint64_t)tok_stride) * 4) || !c->dntok.ensure(std::max<uint64_t>(1, nseg) * 4))
+        return DMX_ERR_NOMEM;
+    HIPCHK(hipMemcpyAsync(c->btab.p, img, bytes, hipMemcpyHostToDevice, st));
+    uint8_t* const dimg = c->btab.as<uint8_t>();
+    DeflateArgs A;
+    A.in = nullptr;
+    A.n = 0;
+    A.nseg = nseg;
+    A.level = level;
+    A.final_last = 1;
+    A.slots = c->slots.as<uint8_t>();
+    A.slot_bytes = slot_bytes;
+    A.tok = c->dtok.as<uint32_t>();
+    A.tok_stride = tok_stride;
+    A.ntok = c->dntok.as<uint32_t>();
+    A.sizes = c->sizes.as<uint32_t>();
+    A.offsets = c->offs.as<uint64_t>();
+    A.total = c->offs.as<uint64_t>() + nseg;  // the scan's total follows the offsets (scan_words)
+    A.out = nullptr;
+    A.cap = 0;
+    A.dbg = nullptr;
+    A.btab = reinterpret_cast<const DeflateBatchSeg*>(dimg);
+    A.bfirst = reinterpret_cast<const uint64_t*>(dimg + off_first);
+    A.bout = reinterpret_cast<uint8_t* const*>(dimg + off_out);
+    A.bcap = reinterpret_cast<const uint64_t*>(dimg + off_cap);
+    A.bres = c->bres.as<dmx_batch_result>();
+    A.nbuf = count;
+    HIPCHK(launch_deflate(A, seg, st, c->timing ? c->ev[1] : nullptr, c->timing ? c->ev[2] : nullptr));
+    HIPCHK(hipEventRecord(c->ev_df, st));
+    c->df_pending = true;
+    HIPCHK(hipMemcpyAsync(res, c->bres.p, count * sizeof(dmx_batch_result), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    end_timing(c, st);
+    c->stats.segments = nseg;
+    for (size_t i = 0; i < count; i++) {
+        c->stats.in_bytes += n[i];
+        c->stats.out_bytes += res[i].bytes;
+    }
+    return DMX_OK;
+}
+
+// Streams above this many compressed bytes leave the batch kernel for the single-stream plan:
+// one wavefront is the wrong tool for a long stream, which the segmented and block-parallel
+// decoders spread over the whole device.  Measured (profiles/batch_probe.json): for
+// ONE stream alone the single-stream plan wins at every probed size (64 KiB of text: 0.32 ms
+// against 7.7 ms on one wavefront), so a latency crossover would lie below the smallest probe;
+// but a routed stream costs ~0.3 ms of serial, host-driven time, and in a batch of many streams
+// the batch kernel wins by throughput (4096 x 64 KiB: 32 ms against 1184 ms for the loop).  The
+// threshold therefore only bounds how long one stream may hold the batch's tail: 1 MiB of
+// compressed input is ~0.3 s on one wavefront.  A rule that weighs the batch's size is the
+// follow-up.
+constexpr size_t kBatchRouteBytes = 1u << 20;
+
+// Batch inflate: k_inflate_batch decodes the streams it keeps, longest first; the routed ones
+// follow through inflate_device_locked, one after another.
+int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count,
+                         uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
+                         hipStream_t st) {
+    std::vector<uint32_t> order, routed;
+    std::vector<uint64_t> image;
+    const size_t off_order = count * sizeof(InflateBatchDesc);
+    try {
+        for (size_t i = 0; i < count; i++) {
+            if ((!d_in[i] && n[i]) || (!d_out[i] && cap[i])) return DMX_ERR_ARG;
+            const bool route = !(flags & DMX_BATCH_NO_ROUTE) && n[i] > kBatchRouteBytes && d_out[i];
+            (route ? routed : order).push_back((uint32_t)i);
+        }
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return n[a] > n[b]; });
+        image.resize((off_order + order.size() * 4 + 7) / 8);
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    static_assert(sizeof(InflateBatchDesc) == 32, "the upload image is built from 8-byte words");
+    uint8_t* const img = reinterpret_cast<uint8_t*>(image.data());
+    InflateBatchDesc* desc = reinterpret_cast<InflateBatchDesc*>(img);
+    for (size_t i = 0; i < count; i++) desc[i] = InflateBatchDesc{d_in[i], n[i], d_out[i], cap[i]};
+    if (!order.empty()) std::memcpy(img + off_order, order.data(), order.size() * 4);
+
+    if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
+    begin_timing(c, st);
+    const size_t res_bytes = count * sizeof(dmx_batch_result);
+    if (!c->btab.ensure(image.size() * 8) || !c->bres.ensure(res_bytes + 16)) return DMX_ERR_NOMEM;
+    HIPCHK(hipMemcpyAsync(c->btab.p, img, image.size() * 8, hipMemcpyHostToDevice, st));
+    if (c->timing) (void)hipEventRecord(c->ev[1], st);
+    HIPCHK(launch_inflate_batch(c->btab.as<InflateBatchDesc>(),
+                                reinterpret_cast<const uint32_t*>(c->btab.as<uint8_t>() + off_order), order.size(),
+                                c->bres.as<dmx_batch_result>(),
+                                reinterpret_cast<unsigned int*>(c->bres.as<uint8_t>() + res_bytes), c->flags, st));
+    if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    HIPCHK(hipEventRecord(c->ev_inf, st));
+    c->inf_pending = true;
+    HIPCHK(hipMemcpyAsync(res, c->bres.p, res_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    end_timing(c, st);
+    const dmx_stats batch_stats = c->stats;
+    for (const uint32_t i : routed) {  // (each call synchronises on its own)
+        size_t len = 0;
+        const int rc = inflate_device_locked(c, d_in[i], n[i], d_out[i], cap[i], &len, nullptr, st);
+        if (rc == DMX_ERR_NOMEM || rc == DMX_ERR_DEVICE) return rc;
+        res[i].bytes = len;
+        res[i].status = rc;
+        res[i].path = c->stats.path;
+    }
+    c->stats = batch_stats;
+    c->stats.segments = count;
+    for (size_t i = 0; i < count; i++) {
+        c->stats.in_bytes += n[i];
+        if (res[i].status == DMX_OK) c->stats.out_bytes += res[i].bytes;
+    }
+    return DMX_OK;
+}
+
 // Adler-32 / CRC-32 of a device buffer, computed on the GPU (checksum.hip); the value is
 // returned to the host (the call synchronizes the stream).
 int checksum_locked(dmx_ctx* c, bool crc, const uint8_t* d, size_t n, uint32_t init, uint32_t* out,
@@ -1611,7 +1773,7 @@ void dmx_destroy(dmx_ctx* c) {
                       &c->ltokoff, &c->lntok, &c->lcaps, &c->lheavy, &c->rtmp, &c->rchain, &c->fbc, &c->fbh, &c->fbo, &c->fbl,
                       &c->fbs, &c->fbt, &c->fbk, &c->fbu, &c->fbch, &c->fbco, &c->fbcs, &c->fbimg, &c->fbstop, &c->fbwin, &c->fbopen, &c->fbvm, &c->fbvh,
                       &c->fbreg, &c->fbJ, &c->fbvis, &c->fbph,
-                      &c->ck})
+                      &c->ck, &c->btab, &c->bres})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1702,6 +1864,112 @@ int dmx_inflate_piece_device(dmx_ctx* c, const void* d_in, size_t n, void* d_out
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return inflate_device_locked(c, (const uint8_t*)d_in, n, (uint8_t*)d_out, cap, out_len, nullptr, st,
                                  DMX_IFLAG_PIECE);
+}
+
+// ---- batched API ---------------------------------------------------------------------------
+// (a context with n_gpus > 1 runs the batch on its own, i.e. its first, device)
+static bool batch_args_ok(const dmx_ctx* c, const void* in, const size_t* n, size_t count, const void* out,
+                          const size_t* cap, const dmx_batch_result* res) {
+    return c && count < (size_t)DF_BATCH_LAST && (count == 0 || (in && n && out && cap && res));
+}
+
+int dmx_deflate_batch_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count, int level,
+                             void* const* d_out, const size_t* cap, dmx_batch_result* res, void* stream) {
+    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res)) return DMX_ERR_ARG;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;  // 64 KiB blocks pair front segments
+    if (count == 0) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return deflate_batch_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), n, count, level,
+                                reinterpret_cast<uint8_t* const*>(d_out), cap, res, st);
+}
+
+int dmx_inflate_batch_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count,
+                             void* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
+                             void* stream) {
+    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res) || (flags & ~DMX_BATCH_NO_ROUTE)) return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return inflate_batch_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), n, count,
+                                reinterpret_cast<uint8_t* const*>(d_out), cap, res, flags, st);
+}
+
+// Host buffers: the inputs are packed into one staging image at 16-byte aligned offsets and go up
+// in one copy; the outputs come back in one copy of the packed output area and are handed out.
+// ocap(i): the device bytes reserved for output i.
+extern "C++" {
+template <class OutCap, class Run>
+static int batch_host(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, uint8_t* const* out,
+                      const size_t* cap, dmx_batch_result* res, OutCap ocap, Run run) {
+    for (size_t i = 0; i < count; i++)
+        if ((!in[i] && n[i]) || (!out[i] && cap[i])) return DMX_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    std::vector<size_t> ioff(count + 1), ooff(count + 1), dcap(count);
+    std::vector<const uint8_t*> din(count);
+    std::vector<uint8_t*> dout(count);
+    std::vector<uint8_t> stage;
+    size_t ti = 0, to = 0;
+    for (size_t i = 0; i < count; i++) {
+        ioff[i] = ti;
+        ooff[i] = to;
+        dcap[i] = ocap(i);
+        ti += (n[i] + 15) & ~size_t(15);
+        to += (dcap[i] + 15) & ~size_t(15);
+    }
+    try {
+        stage.resize(std::max(ti, to));
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    if (!c->in.ensure(ti + 16) || !c->out.ensure(to + 16)) return DMX_ERR_NOMEM;
+    for (size_t i = 0; i < count; i++) {
+        if (n[i]) std::memcpy(stage.data() + ioff[i], in[i], n[i]);
+        din[i] = c->in.as<uint8_t>() + ioff[i];
+        dout[i] = c->out.as<uint8_t>() + ooff[i];
+    }
+    if (ti) HIPCHK(hipMemcpyAsync(c->in.p, stage.data(), ti, hipMemcpyHostToDevice, c->stream));
+    const int rc = run(din.data(), dout.data(), dcap.data());
+    if (rc != DMX_OK) return rc;
+    if (to) HIPCHK(hipMemcpyAsync(stage.data(), c->out.p, to, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < count; i++) {
+        // a result that fits the device area but not the caller's buffer
+        if (res[i].status == DMX_OK && res[i].bytes > cap[i]) res[i].status = DMX_ERR_CAPACITY;
+        const size_t w = std::min<size_t>({(size_t)res[i].bytes, cap[i], dcap[i]});
+        if (w && (res[i].status == DMX_OK || res[i].status == DMX_ERR_CAPACITY))
+            std::memcpy(out[i], stage.data() + ooff[i], w);
+    }
+    return DMX_OK;
+}
+}  // extern "C++"
+
+int dmx_deflate_batch(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, int level,
+                      uint8_t* const* out, const size_t* cap, dmx_batch_result* res) {
+    if (!batch_args_ok(c, in, n, count, out, cap, res)) return DMX_ERR_ARG;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    return batch_host(c, in, n, count, out, cap, res,
+                      [&](size_t i) { return std::min(cap[i], dmx_deflate_bound(n[i])); },
+                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc) {
+                          return deflate_batch_locked(c, di, n, count, level, dou, dc, res, c->stream);
+                      });
+}
+
+int dmx_inflate_batch(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, uint8_t* const* out,
+                      const size_t* cap, dmx_batch_result* res, uint32_t flags) {
+    if (!batch_args_ok(c, in, n, count, out, cap, res) || (flags & ~DMX_BATCH_NO_ROUTE)) return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    return batch_host(c, in, n, count, out, cap, res, [&](size_t i) { return cap[i]; },
+                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc) {
+                          return inflate_batch_locked(c, di, n, count, dou, dc, res, flags, c->stream);
+                      });
 }
 
 int dmx_deflate(dmx_ctx* c, const uint8_t* in, size_t n, int level, uint8_t* out, size_t cap,

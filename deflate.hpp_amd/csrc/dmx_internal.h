@@ -3,7 +3,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/dmx.h"
+
 namespace dmx {
+
+// One segment of a batch: `nb` bytes at `src`; `tail` bytes are readable from src to the end of
+// its buffer (a word read may not run into a neighbour's allocation).
+struct DeflateBatchSeg {
+    const uint8_t* src;
+    uint64_t tail;
+    uint32_t nb;     // <= the context's segment size
+    uint32_t buf;    // buffer index | DF_BATCH_LAST on the last segment of its buffer (BFINAL)
+};
+constexpr uint32_t DF_BATCH_LAST = 1u << 31;
 
 struct DeflateArgs {
     const uint8_t* in;
@@ -22,6 +34,14 @@ struct DeflateArgs {
     uint8_t* out;
     uint64_t cap;
     uint64_t* dbg;        // optional per-block phase timestamps (DMX_PHASES), else nullptr
+    // batch (dmx_deflate_batch_device): the segments come from a table that spans several
+    // buffers instead of from in / n; nullptr otherwise
+    const DeflateBatchSeg* btab = nullptr;  // nseg entries
+    const uint64_t* bfirst = nullptr;     // nbuf + 1: first segment of each buffer (bfirst[nbuf] = nseg)
+    uint8_t* const* bout = nullptr;       // nbuf output pointers
+    const uint64_t* bcap = nullptr;       // nbuf capacities
+    ::dmx_batch_result* bres = nullptr;  // nbuf results, written by k_compact_batch
+    uint64_t nbuf = 0;
 };
 
 // Token words per segment of the front kernel: a literal word covers 1-3 input bytes, a match
@@ -250,5 +270,17 @@ hipError_t launch_segment_check(const InflateArgs& A, const uint64_t* starts, ui
                                 hipStream_t st);
 hipError_t launch_inflate_serial(const InflateArgs& A, int count_only, InflateResult* res,
                                  hipStream_t st);
+
+// batch inflate (inflate_batch.hip): one wavefront per stream on a persistent grid.  order
+// lists the norder streams to decode (indices into desc / res), longest first; workgroups draw
+// positions of it from *ticket (zeroed by the launch).  flags: DMX_CFG_RFC_STRICT.
+struct InflateBatchDesc {
+    const uint8_t* in;
+    uint64_t n;
+    uint8_t* out;
+    uint64_t cap;
+};
+hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
+                                ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st);
 
 }  // namespace dmx

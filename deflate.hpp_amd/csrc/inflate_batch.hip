@@ -1,0 +1,151 @@
+// inflate_batch.hip -- k_inflate_batch: many independent streams per launch, ONE WAVEFRONT PER
+// STREAM (dmx_inflate_batch_device, dmx_batch_result.path 6).
+//
+// Each stream is decoded by the exact decoder inflate_blocks (realDecompress, inflate.hpp:
+// 277-322, with the reference's lenient cases and error semantics) exactly as k_inflate_serial
+// decodes one stream per process -- but a 64-thread workgroup here keeps under 40 KiB of LDS,
+// so four decoders share a CU where the serial kernel's 64 KiB output ring fits two:
+//     output ring   32768 B   the 32 KiB window; flushed to HBM by the whole wave in pieces
+//     input ring     2048 B   RingInT<512, 128>: every bit read is an LDS read
+//     Tables         ~5.6 KB  code tables of the block being decoded
+// The grid is persistent (at most four workgroups per CU): a workgroup draws the next position
+// of `order` from a device ticket until none is left; the host lists the streams longest
+// first, so a long stream starts early and does not form the tail.
+#include "inflate_common.h"
+
+namespace dmx {
+
+constexpr uint32_t BT_RING = 32768;       // output ring bytes = the DEFLATE window
+constexpr uint32_t BT_FLUSH = 16384;      // unflushed bytes that trigger a flush
+constexpr uint32_t BT_RW = 512, BT_RC = 128;  // input ring words, words per slide
+using BatchIn = RingInT<BT_RW, BT_RC>;
+
+// Output sink of one stream, modelled on the serial path's FlushSink with a ring of exactly the
+// window size.  Byte k of the output lives at ring[k % 32768] until byte k + 32768 is written,
+// so before a write every byte it replaces must already be in HBM: pos + L - flushed <= 32768.
+// A literal or a copy adds at most 258 bytes and grown() flushes at 16384 unflushed bytes, so
+// the bound holds with room to spare; a stored block flushes first and writes its bytes to HBM
+// itself.  The window is intact: a copy reads bytes [pos - dist, pos), dist <= 32768, none of
+// which a write at or after pos has replaced -- at dist = 32768 lane i reads and writes the same
+// slot (read first), and for dist just below it the slot lane i reads is written by a later lane
+// of the same wave-wide store, which executes after the wave-wide load.
+// Bytes past `cap` are counted, not written; a distance beyond the stream start copies nothing,
+// as in the reference (inflate.hpp:268-270).
+struct BatchSink {
+    uint8_t* ring;     // BT_RING bytes of LDS
+    uint64_t pos;      // output bytes so far
+    uint64_t flushed;  // bytes [0, min(flushed, cap)) are in `out`
+    uint8_t* out;
+    uint64_t cap;
+    uint32_t err;
+    __device__ bool full() const { return false; }
+    __device__ void flush() {  // [flushed, pos) ring -> out
+        const uint64_t hi = pos < cap ? pos : cap;
+        wave_sync();
+        for (uint64_t i = flushed + lane_id(); i < hi; i += 64) out[i] = ring[i & (BT_RING - 1)];
+        flushed = pos;
+    }
+    __device__ void grown() {
+        if (pos - flushed >= BT_FLUSH) flush();
+    }
+    __device__ bool literal(uint32_t b) {
+        if (lane_id() == 0) ring[pos & (BT_RING - 1)] = (uint8_t)b;
+        pos++;
+        grown();
+        return true;
+    }
+    __device__ bool copy(uint32_t L, uint32_t dist) {
+        if (L == 0 || dist == 0) return true;
+        if (dist > pos) return true;  // reference: nothing to copy (inflate.hpp:268-270)
+        wave_sync();
+        const uint32_t lane = lane_id();
+        const uint64_t src = pos - dist;
+        if (dist >= L || dist >= 64) {  // each group of 64 reads only bytes written before it
+            for (uint32_t i = lane; i < L; i += 64) {
+                ring[(pos + i) & (BT_RING - 1)] = ring[(src + i) & (BT_RING - 1)];
+                wave_sync();
+            }
+        } else {  // periodic: byte i repeats byte i mod dist
+            for (uint32_t i = lane; i < L; i += 64)
+                ring[(pos + i) & (BT_RING - 1)] = ring[(src + i % dist) & (BT_RING - 1)];
+        }
+        wave_sync();
+        pos += L;
+        grown();
+        return true;
+    }
+    // a stored block of up to 65535 bytes: bytes i and i + 32768 share a ring slot and a lane
+    // (32768 % 64 == 0), so the later byte is the one that stays
+    template <class BR>
+    __device__ bool stored(const BR& br, uint64_t b0, uint32_t len) {
+        flush();
+        wave_sync();
+        for (uint32_t i = lane_id(); i < len; i += 64) {
+            const uint8_t v = br.byte_at(b0 + i);
+            ring[(pos + i) & (BT_RING - 1)] = v;
+            if (pos + i < cap) out[pos + i] = v;
+        }
+        wave_sync();
+        pos += len;
+        flushed = pos;
+        return true;
+    }
+};
+
+__global__ __launch_bounds__(IF_NT) void k_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order,
+                                                         uint64_t norder, ::dmx_batch_result* res,
+                                                         unsigned int* ticket, uint32_t flags) {
+    __shared__ __attribute__((aligned(16))) uint8_t ring[BT_RING];
+    __shared__ uint32_t inring[BT_RW];
+    __shared__ Tables T;
+    for (;;) {
+        uint32_t k = 0;
+        if (threadIdx.x == 0) k = atomicAdd(ticket, 1u);
+        k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+        if (k >= norder) break;
+        const uint32_t idx = order[k];
+        const InflateBatchDesc d = desc[idx];
+        ::dmx_batch_result r;
+        r.bytes = 0;
+        r.status = DMX_ERR_OVERREAD;  // an empty input: the reference throws
+        r.path = 6;
+        if (d.n != 0) {
+            if (threadIdx.x == 0) T.fixed_loaded = 0;
+            wave_sync();
+            const uint64_t misalign = reinterpret_cast<uintptr_t>(d.in) & 3;
+            BatchIn br;
+            br.init(reinterpret_cast<const uint32_t*>(d.in - misalign), misalign, d.n, inring);
+            br.seek(misalign * 8);
+            BatchSink sk{ring, 0, 0, d.out, d.cap, 0};
+            uint64_t end_byte = 0;
+            bool fin = false;
+            const uint32_t err = inflate_blocks(br, T, sk, (flags & DMX_CFG_RFC_STRICT) != 0, false, &end_byte, &fin);
+            sk.flush();
+            if (err == 0) {
+                r.bytes = sk.pos;
+                r.status = sk.pos > d.cap ? DMX_ERR_CAPACITY : DMX_OK;
+            } else {
+                r.status = (err & SEGF_OVERREAD) ? DMX_ERR_OVERREAD : DMX_ERR_DATA;
+            }
+        }
+        if (threadIdx.x == 0) res[idx] = r;
+        wave_sync();  // the next stream reuses the rings and tables
+    }
+}
+
+hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
+                                ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st) {
+    if (!norder) return hipSuccess;
+    int dev = 0, ncu = 0, per = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_inflate_batch, IF_NT, 0);
+    const uint64_t fit = (uint64_t)max(ncu, 1) * (uint64_t)max(per, 1);
+    const uint32_t grid = (uint32_t)(norder < fit ? norder : fit);
+    const hipError_t e = hipMemsetAsync(ticket, 0, sizeof(unsigned int), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_inflate_batch, dim3(grid), dim3(IF_NT), 0, st, desc, order, norder, res, ticket, flags);
+    return hipGetLastError();
+}
+
+}  // namespace dmx

@@ -563,11 +563,15 @@ __device__ uint32_t fast_header(const Src& src, uint64_t* pos_io, uint64_t end_b
 // the ring (fast_header reads up to ~140 words past its start).  All lanes call every method
 // together (the decoder state is wave-uniform).
 constexpr uint32_t FB_RW = 1024, FB_RC = 512, FB_AHEAD = 320;
-struct RingIn {
+// RW / RC: the ring's words and the words per slide (RingIn: the serial decoders' 4 KiB ring;
+// the batch decoder takes a smaller one, inflate_batch.hip); RW >= FB_AHEAD + RC + 1
+template <uint32_t RW, uint32_t RC>
+struct RingInT {
+    static_assert(RW >= FB_AHEAD + RC + 1 && RW % 64 == 0 && RC % 64 == 0, "ring too small for the look-ahead");
     const uint32_t* w;
     uint64_t nwords, end_bytes, end_bits;
     uint32_t* ring;
-    uint64_t rb;    // ring holds words [rb, rb + FB_RW) at ring[i % FB_RW]
+    uint64_t rb;    // ring holds words [rb, rb + RW) at ring[i % RW]
     uint64_t pos;   // bits consumed, relative to the aligned base
     uint64_t buf;   // LSB = next bit
     uint32_t cnt;   // valid bits in buf
@@ -589,16 +593,16 @@ struct RingIn {
                 const uint64_t lim = end_bytes - 4 * i;
                 if (lim < 4) v &= (1u << (8 * lim)) - 1u;
             }
-            ring[i % FB_RW] = v;
+            ring[i % RW] = v;
         }
         wave_sync();
     }
-    __device__ uint32_t word(uint64_t i) const { return ring[i % FB_RW]; }
+    __device__ uint32_t word(uint64_t i) const { return ring[i % RW]; }
     __device__ void refill() {
         if (cnt <= 32) {
-            if (wi + FB_AHEAD >= rb + FB_RW) {  // slide: the oldest FB_RC words make room
-                fill(rb + FB_RW, rb + FB_RW + FB_RC);
-                rb += FB_RC;
+            if (wi + FB_AHEAD >= rb + RW) {  // slide: the oldest RC words make room
+                fill(rb + RW, rb + RW + RC);
+                rb += RC;
             }
             buf |= (uint64_t)word(wi) << cnt;
             cnt += 32;
@@ -608,9 +612,9 @@ struct RingIn {
     __device__ void seek(uint64_t bitpos) {
         pos = bitpos;
         const uint64_t i = bitpos >> 5;
-        if (i < rb || i + 1 + FB_AHEAD >= rb + FB_RW) {
+        if (i < rb || i + 1 + FB_AHEAD >= rb + RW) {
             rb = i;
-            fill(i, i + FB_RW);
+            fill(i, i + RW);
         }
         buf = (uint64_t)(word(i) >> (bitpos & 31));
         cnt = 32 - (uint32_t)(bitpos & 31);
@@ -646,11 +650,15 @@ struct RingIn {
         return (uint8_t)(w[b >> 2] >> ((b & 3) * 8));
     }
 };
-struct RingWords {
+using RingIn = RingInT<FB_RW, FB_RC>;
+template <uint32_t RW>
+struct RingWordsT {
     const uint32_t* ring;
-    __device__ uint32_t word(uint64_t i) const { return ring[i % FB_RW]; }
+    __device__ uint32_t word(uint64_t i) const { return ring[i % RW]; }
 };
-__device__ __forceinline__ RingWords reader_words(const RingIn& br) { return RingWords{br.ring}; }
+using RingWords = RingWordsT<FB_RW>;
+template <uint32_t RW, uint32_t RC>
+__device__ __forceinline__ RingWordsT<RW> reader_words(const RingInT<RW, RC>& br) { return RingWordsT<RW>{br.ring}; }
 
 // ---------------------------------------------------------------------------------------
 // lane-parallel token decoding over LDS-staged words (k_inflate_pj, k_fb_pdecode): every lane

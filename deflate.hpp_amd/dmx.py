@@ -25,6 +25,8 @@ DMX_CFG_RFC_STRICT = 1
 DMX_CFG_FB_SERIAL = 2
 DMX_VERIFY = 1
 DMX_DEFLATE_NOT_FINAL = 1
+DMX_BATCH_NO_ROUTE = 1
+BATCH_PATH = 6  # dmx_batch_result.path of a stream the batch decoder took
 
 CORPUS = {"zeros": 0, "repeat": 1, "random": 2, "text": 3, "mixed": 4, "bmp": 5}
 
@@ -37,7 +39,8 @@ EXPORTS = [
     "dmx_framed_bound", "dmx_deflate_zlib", "dmx_deflate_gzip", "dmx_inflate_zlib", "dmx_inflate_gzip",
     "dmx_deflate_file", "dmx_inflate_file", "dmx_segment_starts_device", "dmx_inflate_piece_device",
     "dmx_segment_check_device", "dmx_set_default_config", "dmx_deflate_device_async",
-    "dmx_inflate_device_async",
+    "dmx_inflate_device_async", "dmx_deflate_batch_device", "dmx_inflate_batch_device",
+    "dmx_deflate_batch", "dmx_inflate_batch",
 ]
 
 
@@ -57,6 +60,11 @@ class Stats(ctypes.Structure):
     _fields_ = [("ms_main_kernel", ctypes.c_double), ("ms_device_total", ctypes.c_double),
                 ("segments", ctypes.c_uint64), ("in_bytes", ctypes.c_uint64),
                 ("out_bytes", ctypes.c_uint64), ("path", ctypes.c_uint32), ("shards", ctypes.c_uint32)]
+
+
+class BatchResult(ctypes.Structure):
+    """dmx_batch_result: one buffer's outcome of a batch call."""
+    _fields_ = [("bytes", ctypes.c_uint64), ("status", ctypes.c_int32), ("path", ctypes.c_uint32)]
 
 
 _lib = None
@@ -116,6 +124,11 @@ def lib():
         getattr(L, f).argtypes = [vp, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(sz)]
     for f in ("dmx_inflate_zlib", "dmx_inflate_gzip"):
         getattr(L, f).argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+    brp = ctypes.POINTER(BatchResult)
+    L.dmx_deflate_batch_device.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp, vp, brp, vp]
+    L.dmx_inflate_batch_device.argtypes = [vp, vp, vp, sz, vp, vp, brp, ctypes.c_uint32, vp]
+    L.dmx_deflate_batch.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp, vp, brp]
+    L.dmx_inflate_batch.argtypes = [vp, vp, vp, sz, vp, vp, brp, ctypes.c_uint32]
     _lib = L
     return L
 
@@ -366,6 +379,62 @@ class Context:
         _check(lib().dmx_segment_starts_device(self.h, ctypes.c_void_p(d_in), n, buf, cnt.value, ctypes.byref(cnt),
                                                sp), "segment_starts")
         return list(buf[: cnt.value])
+
+    # ---- batched API: many independent buffers per call -----------------------------------
+    @staticmethod
+    def _batch_arrays(ptrs, sizes, out_ptrs, caps):
+        k = len(ptrs)
+        if not (len(sizes) == len(out_ptrs) == len(caps) == k):
+            raise ValueError("batch arrays differ in length")
+        m = max(1, k)
+        return (k, (ctypes.c_void_p * m)(*ptrs), (ctypes.c_size_t * m)(*sizes), (ctypes.c_void_p * m)(*out_ptrs),
+                (ctypes.c_size_t * m)(*caps), (BatchResult * m)())
+
+    def deflate_batch_device(self, ptrs, sizes, level, out_ptrs, caps, stream=None):
+        """dmx_deflate_batch_device: device pointers / sizes per buffer -> [(bytes, status, path)].
+        Buffer i gets exactly the stream deflate_device writes for it alone."""
+        k, a_in, a_n, a_out, a_cap, res = self._batch_arrays(ptrs, sizes, out_ptrs, caps)
+        _check(lib().dmx_deflate_batch_device(self.h, a_in, a_n, k, level, a_out, a_cap, res,
+                                              ctypes.c_void_p(stream) if stream else None), "deflate_batch_device")
+        return [(r.bytes, r.status, r.path) for r in res[:k]]
+
+    def inflate_batch_device(self, ptrs, sizes, out_ptrs, caps, stream=None, no_route=False):
+        """dmx_inflate_batch_device -> [(bytes, status, path)]; no_route: every stream on the
+        batch decoder, however long (developer A/B)."""
+        k, a_in, a_n, a_out, a_cap, res = self._batch_arrays(ptrs, sizes, out_ptrs, caps)
+        _check(lib().dmx_inflate_batch_device(self.h, a_in, a_n, k, a_out, a_cap, res,
+                                              DMX_BATCH_NO_ROUTE if no_route else 0,
+                                              ctypes.c_void_p(stream) if stream else None), "inflate_batch_device")
+        return [(r.bytes, r.status, r.path) for r in res[:k]]
+
+    def _batch_host(self, fn, datas, caps, mid=(), tail=()):
+        datas = [bytes(d) for d in datas]
+        k = len(datas)
+        ins = [ctypes.create_string_buffer(d, max(1, len(d))) for d in datas]
+        outs = [ctypes.create_string_buffer(max(1, c)) for c in caps]
+        _, a_in, a_n, a_out, a_cap, res = self._batch_arrays(
+            [ctypes.addressof(b) for b in ins], [len(d) for d in datas], [ctypes.addressof(b) for b in outs], caps)
+        args = (self.h, a_in, a_n, k) + mid + (a_out, a_cap, res) + tail
+        _check(getattr(lib(), fn)(*args), fn)
+        return outs, res[:k]
+
+    def compress_batch(self, datas, level=2):
+        """Raw DEFLATE stream of every buffer in one call: equal to [compress(d, level) ...]."""
+        outs, res = self._batch_host("dmx_deflate_batch", datas, [deflate_bound(len(d)) for d in datas], mid=(level,))
+        for r in res:
+            _check(r.status, "deflate_batch")
+        return [o.raw[: r.bytes] for o, r in zip(outs, res)]
+
+    def decompress_batch(self, datas, caps, no_route=False, with_results=False):
+        """Inflate every stream in one call.  caps[i] bounds output i; each element is the
+        decoded bytes, or the DmxError that decompress would raise for that stream alone
+        (DMX_ERR_CAPACITY when it needs more than caps[i]).  with_results: also the list of
+        (bytes, status, path) per stream."""
+        outs, res = self._batch_host("dmx_inflate_batch", datas, list(caps),
+                                     tail=(DMX_BATCH_NO_ROUTE if no_route else 0,))
+        vals = [o.raw[: r.bytes] if r.status == DMX_OK else DmxError(r.status, "inflate_batch")
+                for o, r in zip(outs, res)]
+        return (vals, [(r.bytes, r.status, r.path) for r in res]) if with_results else vals
 
     def set_timing(self, on=True):
         _check(lib().dmx_set_timing(self.h, 1 if on else 0), "set_timing")

@@ -200,6 +200,57 @@ int dmx_inflate_piece_device(dmx_ctx* ctx, const void* d_in, size_t n, void* d_o
 int dmx_segment_check_device(dmx_ctx* ctx, const void* d_in, size_t n, const uint64_t* starts, size_t k,
                              uint64_t* ends, void* stream);
 
+/* ---- batched API: many independent buffers per call (not in the reference) ----------------
+ * Every entry point above takes one buffer and pays a fixed cost per call (kernel launches,
+ * host synchronisations).  These take `count` independent buffers and cover all of them with
+ * one set of launches.
+ *
+ * Return value: the call as a whole -- DMX_ERR_ARG (null context or array, unsupported
+ * option), DMX_ERR_NOMEM or DMX_ERR_DEVICE.  A bad stream or a short cap[i] is reported only in
+ * res[i] and never disturbs its neighbours; count == 0 is DMX_OK.
+ *
+ * Deflate: stream i is exactly the bytes dmx_deflate_device(ctx, d_in[i], n[i], level, 0, ...)
+ * writes: a complete stream with BFINAL (an empty input gives 03 00); dmx_deflate_bound(n[i])
+ * bounds it.  When cap[i] is too small, status = DMX_ERR_CAPACITY, bytes = the size that was
+ * needed, and nothing is written past d_out[i] + cap[i].  Contexts with segment_bytes of 16 or
+ * 32 KiB are supported; a context with segment_bytes = 65536 returns DMX_ERR_ARG (its emit
+ * stage codes front segments 2s and 2s + 1 as one block, a pairing that does not survive buffer
+ * boundaries).
+ *
+ * Inflate: the per-stream result equals dmx_inflate_device on that stream alone -- any RFC 1951
+ * stream, the reference's lenient cases and the A-11/A-12 quirks included (DMX_CFG_RFC_STRICT of
+ * the context is honoured), and the same codes: DMX_ERR_OVERREAD for n[i] == 0 or a truncated
+ * stream, DMX_ERR_DATA, DMX_ERR_CAPACITY.  With DMX_ERR_CAPACITY from the batch decoder, bytes
+ * = the full decoded size and the first cap[i] bytes are written.  One wavefront decodes one
+ * stream; streams with n[i] above a built-in threshold go through the single-stream plan
+ * instead, one after another (their `path` tells), unless DMX_BATCH_NO_ROUTE is set.
+ *
+ * Both calls take the context mutex, are ordered against the context's other deflate / inflate
+ * work like their single-buffer siblings, and end with one host synchronisation, the read-back
+ * of res (routed inflate streams add the single-stream plan's own).  A context with n_gpus > 1
+ * runs the batch on its first device. */
+typedef struct dmx_batch_result {
+    uint64_t bytes;   /* produced bytes; on DMX_ERR_CAPACITY the size that was needed */
+    int32_t status;   /* DMX_OK or DMX_ERR_* for this buffer alone */
+    uint32_t path;    /* inflate: 6 = batch decoder (one wavefront per stream), else the
+                         dmx_stats.path value of the single-stream plan it was routed to;
+                         deflate: 0 */
+} dmx_batch_result;
+
+/* device-resident: HOST arrays of DEVICE pointers / sizes, `count` entries each */
+int dmx_deflate_batch_device(dmx_ctx* ctx, const void* const* d_in, const size_t* n, size_t count,
+                             int level, void* const* d_out, const size_t* cap,
+                             dmx_batch_result* res, void* stream);
+#define DMX_BATCH_NO_ROUTE 1u /* developer A/B: decode every stream on the batch kernel */
+int dmx_inflate_batch_device(dmx_ctx* ctx, const void* const* d_in, const size_t* n, size_t count,
+                             void* const* d_out, const size_t* cap, dmx_batch_result* res,
+                             uint32_t flags, void* stream);
+/* host buffers: the same with host pointers (one staged H2D, one D2H) */
+int dmx_deflate_batch(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, size_t count, int level,
+                      uint8_t* const* out, const size_t* cap, dmx_batch_result* res);
+int dmx_inflate_batch(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, size_t count,
+                      uint8_t* const* out, const size_t* cap, dmx_batch_result* res, uint32_t flags);
+
 /* ---- checksums and containers (not in the reference) -------------------
  * The reference's decompressZlib (inflate.hpp:326-361) skips the 2-byte header and ignores the
  * Adler-32 (SURVEY A-9); inflate.hpp's decompressZlib keeps exactly that.  These entry points
@@ -247,7 +298,9 @@ typedef struct dmx_stats {
                                5 = block-parallel decoder for streams without segment
                                    markers (zlib's, libdeflate's, the reference's own):
                                    header scan, one wavefront per unit of blocks, window
-                                   hand-off                                                  */
+                                   hand-off,
+                               6 = batch decoder, one wavefront per stream (reported in
+                                   dmx_batch_result.path only; dmx_stats.path never holds it) */
     uint32_t shards;        /* host-buffer API with n_gpus > 1: the pieces the call was split
                                into (0 or 1: one device)                                       */
 } dmx_stats;

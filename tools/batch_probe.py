@@ -1,0 +1,146 @@
+"""Measurement of the batched API (GPU only; fails without a device).  Writes
+profiles/batch_probe.json, which DESIGN quotes.
+
+1. batch against loop: 16384 x 4 KiB and 4096 x 64 KiB buffers of text and of mixed data,
+   level 2, deflate and inflate; one batch call against a loop of deflate_device /
+   inflate_device over the same device buffers, the two alternated within the run.
+2. routing crossover: single libdmx level-2 text streams of 64 KiB .. 16 MiB,
+   inflate_batch_device(no_route=True) against inflate_device.
+
+Timing: synchronised host wall clock around each call (every call ends in a host
+synchronisation of its own), WARM warm-up repetitions, then REPS measured ones; the median is
+reported with the minimum beside it.
+
+  python tools/batch_probe.py [--reps 20] [--quick]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "deflate.hpp_amd"))
+import torch  # noqa: E402
+
+import dmx  # noqa: E402
+
+WARM = 2
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1e3
+
+
+def alternate(a, b, reps):
+    """Run a and b alternately: WARM unmeasured rounds, then reps measured ones."""
+    ta, tb = [], []
+    for k in range(WARM + reps):
+        x, y = timed(a), timed(b)
+        if k >= WARM:
+            ta.append(x)
+            tb.append(y)
+    return ta, tb
+
+
+def summary(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "reps": len(ms)}
+
+
+def batch_vs_loop(ctx, kind, count, size, reps):
+    data = dmx.corpus(kind, count * size, offset=1 << 20)
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    bound = (dmx.deflate_bound(size) + 15) & ~15
+    d_c = torch.empty(count * bound, dtype=torch.uint8, device="cuda")
+    d_o = torch.empty(count * size, dtype=torch.uint8, device="cuda")
+    ins = [d_in.data_ptr() + i * size for i in range(count)]
+    comps = [d_c.data_ptr() + i * bound for i in range(count)]
+    outs = [d_o.data_ptr() + i * size for i in range(count)]
+    sizes, bounds = [size] * count, [bound] * count
+    clen = []
+
+    def df_batch():
+        clen[:] = [r[0] for r in ctx.deflate_batch_device(ins, sizes, 2, comps, bounds)]
+
+    def df_loop():
+        for i in range(count):
+            ctx.deflate_device(ins[i], size, 2, comps[i], bound)
+
+    def if_batch():
+        res = ctx.inflate_batch_device(comps, clen, outs, sizes)
+        assert all(r[1] == dmx.DMX_OK for r in res)
+
+    def if_loop():
+        for i in range(count):
+            ctx.inflate_device(comps[i], clen[i], outs[i], size)
+
+    db, dl = alternate(df_batch, df_loop, reps)
+    ib, il = alternate(if_batch, if_loop, reps)
+    assert d_o.cpu().numpy().tobytes() == data, "round trip mismatch"
+    row = {"kind": kind, "count": count, "size": size, "compressed_bytes": sum(clen),
+           "deflate_batch": summary(db), "deflate_loop": summary(dl),
+           "inflate_batch": summary(ib), "inflate_loop": summary(il)}
+    row["deflate_loop_over_batch"] = row["deflate_loop"]["median_ms"] / row["deflate_batch"]["median_ms"]
+    row["inflate_loop_over_batch"] = row["inflate_loop"]["median_ms"] / row["inflate_batch"]["median_ms"]
+    return row
+
+
+def crossover(ctx, size, reps):
+    data = dmx.corpus("text", size, offset=7 << 20)
+    s = ctx.compress(data, 2)
+    d_s = torch.frombuffer(bytearray(s), dtype=torch.uint8).cuda()
+    d_o = torch.empty(size, dtype=torch.uint8, device="cuda")
+
+    def one_wave():
+        res = ctx.inflate_batch_device([d_s.data_ptr()], [len(s)], [d_o.data_ptr()], [size], no_route=True)
+        assert res[0] == (size, dmx.DMX_OK, dmx.BATCH_PATH), res
+
+    def single():
+        assert ctx.inflate_device(d_s.data_ptr(), len(s), d_o.data_ptr(), size) == size
+
+    tb, ts = alternate(one_wave, single, reps)
+    assert d_o.cpu().numpy().tobytes() == data
+    return {"plain_bytes": size, "stream_bytes": len(s), "batch_kernel": summary(tb), "inflate_device": summary(ts),
+            "batch_kernel_wins": statistics.median(tb) < statistics.median(ts)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--quick", action="store_true", help="an eighth of the buffer counts (a check of the tool)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_probe.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("batch_probe: no GPU")
+    ctx = dmx.Context()
+    q = 8 if a.quick else 1
+    result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
+              "timing": "synchronised host wall clock per call, batch and loop alternated",
+              "batch_vs_loop": [], "routing_crossover": []}
+    def save():  # after every row: a run cut short still leaves what it measured
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+    # the cheap parts first: the 4 KiB loops take minutes (16384 single calls per repetition)
+    for size in (64 << 10, 256 << 10, 1 << 20, 4 << 20, 16 << 20):
+        row = crossover(ctx, size, a.reps)
+        result["routing_crossover"].append(row)
+        print(json.dumps(row), flush=True)
+        save()
+    for count, size in ((4096 // q, 65536), (16384 // q, 4096)):
+        for kind in ("text", "mixed"):
+            row = batch_vs_loop(ctx, kind, count, size, a.reps)
+            result["batch_vs_loop"].append(row)
+            print(json.dumps(row), flush=True)
+            save()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
