@@ -92,6 +92,13 @@ constexpr uint32_t DF_L3_RP = DMX_L3_RP;
 #define DMX_DF_SKIP 1
 #endif
 constexpr bool DF_SKIP = DMX_DF_SKIP != 0;
+// level 2: a run that the continuation test verifies up to the segment end (a terminal run)
+// ends the match rounds: its candidates are stored by one vector-store loop and the match
+// bitmap of its positions is written as ones (see run_lo).  0: every remaining round stores
+// its candidates and the bitmap is built from them
+#ifndef DMX_DF_TERMRUN
+#define DMX_DF_TERMRUN 1
+#endif
 // the front kernel counts the symbols (the emission kernel skips its histogram pass)
 #ifndef DMX_DF_HIST
 #define DMX_DF_HIST 0
@@ -537,6 +544,10 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
     const uint32_t nb = sa.nb;
     constexpr int level = L3 ? 3 : 2;  // (the front kernel runs at levels 2 and 3 only)
     uint8_t* const dbytes = reinterpret_cast<uint8_t*>(S.data32);
+    // (32 KiB segments only: the 16 KiB kernel sits at its 64-register limit, and with this code
+    // in it the compiler spills its kernel arguments to scratch)
+    constexpr bool TERMRUN = DF_SKIP && !L3 && SEG >= 32768 && DMX_DF_TERMRUN;
+    constexpr uint32_t RUN_NONE = 0xFFFFFFFFu;
     DMX_PHASE(A.dbg, seg, 0);
 
     // ---- load the segment into LDS (16 B per lane when aligned) ------------------------
@@ -556,6 +567,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         for (uint32_t i = nb + t; i < ((nb + 3) & ~3u) + 32; i += DF_NT) dbytes[i] = 0;
         if (t < NMAP) S.tokmap[t] = 0;
         if (t == 0) S.sh[46] = 0;  // the match rounds' mismatch tag (run continuation)
+        if (TERMRUN && t == 1) S.sh[45] = RUN_NONE;  // its terminal run's first position
         if (t >= 48 && t < 63) S.sh[t] = 0;  // its divisor-period tags
         if (DMX_DF_HIST && t < 320) S.hist[t] = 0;
         if (level >= 2)
@@ -567,6 +579,11 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
 
     if (level != 0) {
         bool any_skip = false;  // (uniform) the run continuation took a round of this segment
+        // Terminal run (uniform): the positions [run_lo, nb) repeat at distance run_d up to the
+        // segment end, so every one of them with four bytes left has the candidate run_d.  The
+        // match rounds end at run_lo (a round's first position).  The round that finds the run
+        // leaves both values in sh[45] and sh[47]: the rounds' loop carries no state for them.
+        [[maybe_unused]] uint32_t run_lo = RUN_NONE, run_d = 0;
         // ---- match candidates: rounds of 2*DF_NT positions, two per thread ---------------
         if (level >= 2) {
             // Table entries carry a fingerprint of the 4-byte key (product bits below the hash
@@ -676,7 +693,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         constexpr bool FULL = decltype(full)::value;
                         const uint32_t p0 = r0 + 2 * tt, p1 = p0 + 1;
                         if (SKIP && skip_d) {
-                            if (r0 + RP <= skip_end || skip_end >= nb) {  // inside the verified run
+                            if (r0 + RP <= skip_end || (!TERMRUN && skip_end >= nb)) {  // inside the verified run
                                 if (FULL || p0 < nb)
                                     cand32[p0 >> 1] = (FULL || p0 + 4 <= nb ? skip_d : 0u) |
                                                       ((FULL || p1 + 4 <= nb ? skip_d : 0u) << 16);
@@ -769,7 +786,15 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
 #ifdef DMX_DF_SKIPDBG
                             if (seg == 10 && t == 0) printf("seg %u round %u tested m %u skip_end %u\n", (unsigned)seg, rr, m, skip_end);
 #endif
-                            if (r0 + RP <= skip_end || skip_end >= nb) {  // this round is inside the run
+                            if (TERMRUN && skip_end >= nb) {  // a terminal run: the rounds end here
+                                if (t == 0) {                  // (see run_lo)
+                                    S.sh[45] = r0;
+                                    S.sh[47] = skip_d;
+                                }
+                                skipped = true;
+                                return;
+                            }
+                            if (r0 + RP <= skip_end || (!TERMRUN && skip_end >= nb)) {  // this round is inside the run
                                 if (act && (FULL || p0 < nb))
                                     cand32[p0 >> 1] = (ok0 ? skip_d : 0u) | ((ok1 ? skip_d : 0u) << 16);
                                 cur = RoundState{NOH, NOH, p0, 0, 0, false, false};
@@ -812,13 +837,16 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     const DeflateArgs& Ar = A;  // (shadowed by the round states below)
                     RoundState A = {0, 0, 0, 0, 0, false, false}, B = A;
                     uint32_t r0 = 0, rr = 0;
-                    for (; r0 + 2 * RP + 3 <= nb; r0 += 2 * RP, rr += 2) {  // two full rounds
+                    // (a terminal run ends the rounds: skip_end >= nb only then)
+                    auto more = [&]() { return !(TERMRUN && SKIP) || skip_end < nb; };
+                    for (; r0 + 2 * RP + 3 <= nb && more(); r0 += 2 * RP, rr += 2) {  // two full rounds
                         round(r0, rr, A, B, Full{});
                         if (rr == 0) DMX_PHASE(Ar.dbg, seg, 12);
+                        if (!more()) break;
                         round(r0 + RP, rr + 1, B, A, Full{});
                         if (rr == 0) DMX_PHASE(Ar.dbg, seg, 13);
                     }
-                    for (; r0 < nb; r0 += RP, rr++) {  // the rest (the last may be partial)
+                    for (; r0 < nb && more(); r0 += RP, rr++) {  // the rest (the last may be partial)
                         round(r0, rr, A, B, Part{});
                         const RoundState x = A;
                         A = B;
@@ -831,6 +859,10 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     run_rounds(std::integral_constant<uint32_t, 2 * DF_NT>{});
                 if (DF_SKIP && skipped) __syncthreads();  // skipped rounds end without a barrier
                 any_skip = skipped;
+                if (TERMRUN && skipped) {
+                    run_lo = __builtin_amdgcn_readfirstlane(S.sh[45]);
+                    run_d = __builtin_amdgcn_readfirstlane(S.sh[47]);
+                }
             }
             DMX_PHASE(A.dbg, seg, 14);
         }
@@ -902,6 +934,13 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         if (level >= 2) {
             // match bitmap from the candidates: bit p = "a candidate starts at p"
             for (uint32_t w = t; w < NMAP; w += DF_NT) {
+                if (TERMRUN && 32 * w >= run_lo) {
+                    // the terminal run (run_lo is a multiple of 32): every position with four
+                    // bytes left has the candidate run_d
+                    const uint32_t b0 = 32 * w;
+                    S.mmap[w] = nb >= b0 + 35 ? 0xFFFFFFFFu : (nb > b0 + 3 ? (1u << (nb - 3 - b0)) - 1u : 0u);
+                    continue;
+                }
                 const uint4* c4 = reinterpret_cast<const uint4*>(S.cand + 32 * w);
                 uint32_t m = 0;
 #pragma unroll
@@ -916,6 +955,16 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 }
                 const uint32_t b0 = 32 * w;  // positions past the segment end hold stale entries
                 S.mmap[w] = b0 + 32 <= nb ? m : (nb > b0 ? m & ((1u << (nb - b0)) - 1u) : 0u);
+            }
+            if (TERMRUN && run_lo != RUN_NONE) {
+                // the terminal run's candidates (nb > run_lo >= 2 * DF_NT): eight positions per
+                // store while all eight have four bytes left, then the last 3..10 one by one
+                const uint32_t v = run_d | (run_d << 16);
+                const uint32_t i0 = run_lo / 8, i1 = max(i0, (nb - 11) / 8 + 1);
+                uint4* const c4 = reinterpret_cast<uint4*>(S.cand);
+                for (uint32_t i = i0 + t; i < i1; i += DF_NT) c4[i] = make_uint4(v, v, v, v);
+                const uint32_t p = 8 * i1 + t;
+                if (t < 16 && p < nb) S.cand[p] = (uint16_t)(p + 4 <= nb ? run_d : 0u);
             }
             __syncthreads();
         }
