@@ -460,21 +460,32 @@ struct DfSmem {
 // __syncthreads waits for it (an LDS-DMA load counts on vmcnt).
 // Where segment `seg` of SEG bytes lies.  One stream (BATCH false): computed from A.in / A.n.
 // A batch: read from the segment table (A.btab), whose entries span several buffers.
+// DICT (a batch with a preset dictionary): also the dictionary bytes that precede the segment's
+// own in the front kernel's image (DeflateBatchSeg); every other caller sees dlen = 0.
 struct DfSegAddr {
     const uint8_t* src;  // the segment's first byte
     uint64_t tail;       // bytes readable from src (to the end of the segment's own buffer)
     uint32_t nb;         // the segment's bytes (<= SEG)
     bool is_last;        // the last segment of its stream (BFINAL when the stream is final)
+    const uint8_t* dict;  // the dlen dictionary bytes before it (dlen + nb <= SEG)
+    uint32_t dlen;
 };
-template <int SEG, bool BATCH>
+template <int SEG, bool BATCH, bool DICT = false>
 __device__ __forceinline__ DfSegAddr df_seg_addr(const DeflateArgs& A, uint64_t seg) {
+    static_assert(!DICT || BATCH, "the dictionary comes with the batch's segment table");
     DfSegAddr s;
+    s.dict = nullptr;
+    s.dlen = 0;
     if constexpr (BATCH) {
         const DeflateBatchSeg e = A.btab[seg];
         s.src = e.src;
         s.tail = e.tail;
         s.nb = e.nb;
         s.is_last = (e.buf & DF_BATCH_LAST) != 0;
+        if constexpr (DICT) {
+            s.dict = e.dict;
+            s.dlen = (uint32_t)e.dlen;
+        }
     } else {
         const uint64_t base = seg * (uint64_t)SEG;
         s.src = A.in + base;
@@ -485,7 +496,7 @@ __device__ __forceinline__ DfSegAddr df_seg_addr(const DeflateArgs& A, uint64_t 
     return s;
 }
 
-template <int SEG, bool BATCH>
+template <int SEG, bool BATCH, bool DICT = false>
 __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t seg, DfSmem<SEG>& S) {
     bool go;
     const uint8_t* nsrc;
@@ -495,6 +506,8 @@ __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t 
             const DeflateBatchSeg e = A.btab[seg + gridDim.x];
             nsrc = e.src;
             go = e.nb == (uint32_t)SEG && ((reinterpret_cast<uintptr_t>(nsrc) & 15) == 0);
+            // (a dictionary segment's bytes do not start at the image's first byte: never staged)
+            if constexpr (DICT) go = go && e.dlen == 0;
         } else {
             nsrc = nullptr;
         }
@@ -533,15 +546,37 @@ __device__ __forceinline__ uint32_t next_tok(const uint32_t* tokmap, uint32_t& w
 
 // L3: level 3 (chain search, lazy parse) -- a separate instantiation, so the level-2 kernel
 // carries none of that code (the 1024-thread kernel's register allocation and code size)
-template <int SEG, bool L3, bool BATCH>
+// n bytes from HBM to the LDS image at byte offset off: 16 B per lane where the source and the
+// image offset are congruent mod 16, bytes otherwise (and at the ends)
+__device__ __forceinline__ void df_load_at(uint8_t* dbytes, uint32_t off, const uint8_t* src, uint32_t n, int t) {
+    uint32_t head = (16u - (off & 15u)) & 15u;
+    if (((reinterpret_cast<uintptr_t>(src) + head) & 15) != 0 || head > n) head = n;
+    for (uint32_t i = t; i < head; i += DF_NT) dbytes[off + i] = src[i];
+    const uint32_t nvec = (n - head) / 16;
+    const uint4* s4 = reinterpret_cast<const uint4*>(src + head);
+    uint4* d4 = reinterpret_cast<uint4*>(dbytes + off + head);
+    for (uint32_t i = t; i < nvec; i += DF_NT) d4[i] = s4[i];
+    for (uint32_t i = head + 16 * nvec + t; i < n; i += DF_NT) dbytes[off + i] = src[i];
+}
+
+// DICT: a batch with a preset dictionary (DeflateBatchSeg).  The image of a buffer's first
+// segment is [D dictionary bytes | the segment's bytes]: the match rounds (and level 3's chain
+// search) run over all of it, so dictionary positions enter the hash tables and may be match
+// sources, but the parse walk and its chunks start at D: tokens, their counts and the histogram
+// cover the segment's own bytes only.  A match's distance is its distance in the image -- the D
+// bytes are the last of the dictionary, which the decoder's window holds just before the
+// stream's first byte.  Below, nb is the image's length and D the first position with a token;
+// without DICT (and for the later segments of a buffer) D = 0 and nb = the segment's bytes.
+template <int SEG, bool L3, bool BATCH, bool DICT>
 __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG>& S, uint64_t seg,
                                                 bool& staged) {
     [[maybe_unused]] constexpr int NWALK = DfSmem<SEG>::NWALK;
     constexpr int HT = DfSmem<SEG>::HT;
     constexpr int NMAP = SEG / 32;
     const int t = df_tid();
-    const DfSegAddr sa = df_seg_addr<SEG, BATCH>(A, seg);
-    const uint32_t nb = sa.nb;
+    const DfSegAddr sa = df_seg_addr<SEG, BATCH, DICT>(A, seg);
+    const uint32_t D = DICT ? sa.dlen : 0u;
+    const uint32_t nb = D + sa.nb;
     constexpr int level = L3 ? 3 : 2;  // (the front kernel runs at levels 2 and 3 only)
     uint8_t* const dbytes = reinterpret_cast<uint8_t*>(S.data32);
     // (32 KiB segments only: the 16 KiB kernel sits at its 64-register limit, and with this code
@@ -555,6 +590,9 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         const uint8_t* src = sa.src;
         const uint32_t nvec = nb / 16;
         if (staged) {  // loaded during the previous segment (df_prefetch_next)
+        } else if (DICT && D) {
+            df_load_at(dbytes, 0, sa.dict, D, t);
+            df_load_at(dbytes, D, src, nb - D, t);
         } else if ((((uintptr_t)src) & 15) == 0) {
             const uint4* s4 = reinterpret_cast<const uint4*>(src);
             uint4* d4 = reinterpret_cast<uint4*>(S.data32);
@@ -883,9 +921,10 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             for (int k = 0; k < KP; k++) {
                 const uint32_t p = t + DF_NT * k;
                 uint32_t bd = 0;
-                const uint32_t d0 = p < nb ? S.cand[p] : 0u;
+                // (dictionary positions start no token: their links are only walked through)
+                const uint32_t d0 = p < nb && (!DICT || p >= D) ? S.cand[p] : 0u;
                 if (d0) {
-                    const uint32_t hi = min(p / DF_CHUNK * DF_CHUNK + DF_CHUNK, nb);
+                    const uint32_t hi = min(D + (p - D) / DF_CHUNK * DF_CHUNK + DF_CHUNK, nb);
                     const uint32_t maxl = min(258u, hi - p);
                     // The first link: its length up to DF_L3_LONG bytes; a first link that long
                     // ends the search (periodic data, an image row: every link is that long,
@@ -977,11 +1016,11 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // continuation: short matches, text-like) is parsed in half-size chunks, twice the
         // walkers; a segment with one keeps 258-byte chunks, whose matches reach the maximum
         const uint32_t CH = (DMX_DF_ADAPT && level == 2 && !any_skip) ? (uint32_t)DF_CHUNK / 2 : (uint32_t)DF_CHUNK;
-        const uint32_t nwalk = (nb + CH - 1) / CH;
+        const uint32_t nwalk = (nb - D + CH - 1) / CH;  // (the chunks start at D)
         if (level >= 2 && (uint32_t)t < 4 * nwalk) {
             const uint32_t sub = t & 3;
             const bool lead = sub == 0;
-            const uint32_t lo = (t >> 2) * CH;
+            const uint32_t lo = D + (t >> 2) * CH;
             const uint32_t hi = min(lo + CH, nb);
             auto bits_range = [](uint32_t a, uint32_t b, uint32_t w) -> uint32_t {  // [a, b) in word w
                 const uint32_t e = b - w * 32;
@@ -1126,7 +1165,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // edges are independent.
         if (level >= 2) {
             const uint32_t sub = t & 3, c = t >> 2;
-            const uint32_t hb = (c + 1) * CH;  // the edge
+            const uint32_t hb = D + (c + 1) * CH;  // the edge
             if ((uint32_t)t < 4 * (nwalk - 1) && hb < nb) {
                 const uint32_t s0 = S.lasttok[c], d0 = S.cand[s0], L0 = S.cand[s0 + 1];
                 const uint32_t sn = S.lasttok[c + 1];  // the extension ends before it
@@ -1219,10 +1258,12 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         //      bytes per word, one word per match (count, block scan of the counts, write).  A
         //      segment without a match (every position a token: incompressible data) writes none:
         //      the emission kernel reads its literals from the input -----
-        const bool all_lit = tr_total == nb;
+        const bool all_lit = tr_total == nb - D;
         if (all_lit) {
             if (t == 0) A.ntok[seg] = EM_ALL_LITERALS;
-            if (DMX_DF_HIST)  // the literal histogram, four bytes per word
+            if (DMX_DF_HIST && DICT) {  // (the segment's own bytes start at D, any alignment)
+                for (uint32_t i = D + t; i < nb; i += DF_NT) atomicAdd(&S.hist[dbytes[i]], 1u);
+            } else if (DMX_DF_HIST)  // the literal histogram, four bytes per word
                 for (uint32_t i = t; 4 * i < nb; i += DF_NT) {
                     const uint32_t x = S.data32[i];
 #pragma unroll
@@ -1277,7 +1318,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         __syncthreads();  // every read of the segment's bytes is done
         if (DMX_DF_HIST && t < (int)kDeflateHistWords)
             A.tok[seg * (uint64_t)A.tok_stride + A.tok_stride - kDeflateHistWords + t] = S.hist[2 * t] | (S.hist[2 * t + 1] << 16);
-        staged = df_prefetch_next<SEG, BATCH>(A, seg, S);
+        staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, S);
         DMX_PHASE(A.dbg, seg, 10);
     }
 }
@@ -1287,25 +1328,27 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
 // registers per lane, which amdgpu_waves_per_eu(8) asks for.
 // Persistent workgroups (as many as fit the GPU at once): workgroup b compresses segments
 // b, b + G, b + 2G, ... and loads each next segment while it works on the current one.
-template <int SEG, bool L3, bool BATCH>
+template <int SEG, bool L3, bool BATCH, bool DICT>
 __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SEG>& S) {
     bool staged = false;  // S.data32 already holds the segment's bytes
     for (uint64_t seg = blockIdx.x; seg < A.nseg; seg += gridDim.x) {
-        deflate_segment<SEG, L3, BATCH>(A, S, seg, staged);
+        deflate_segment<SEG, L3, BATCH, DICT>(A, S, seg, staged);
         __syncthreads();  // the next segment reuses the LDS (and its prefetch has landed)
     }
 }
 // BATCH: the segments come from the batch's segment table (df_seg_addr); the default
-// instantiations are the single-stream kernels
-template <int SEG, bool L3, bool BATCH = false>
+// instantiations are the single-stream kernels.  DICT: the table's segments may carry a preset
+// dictionary (deflate_segment); 32 KiB segments only -- the 16 KiB kernel has neither the
+// registers nor the image room for it.
+template <int SEG, bool L3, bool BATCH = false, bool DICT = false>
 __global__ __launch_bounds__(DF_NT) void k_deflate_segments(DeflateArgs A) {
     __shared__ DfSmem<SEG> S;
-    deflate_segments<SEG, L3, BATCH>(A, S);
+    deflate_segments<SEG, L3, BATCH, DICT>(A, S);
 }
 template <bool L3, bool BATCH = false>
 __global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_deflate_segments16(DeflateArgs A) {
     __shared__ DfSmem<16384> S;
-    deflate_segments<16384, L3, BATCH>(A, S);
+    deflate_segments<16384, L3, BATCH, false>(A, S);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2126,7 +2169,8 @@ __global__ __launch_bounds__(256) void k_compact_batch(DeflateArgs A) {
 }
 
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st,
-                          hipEvent_t ev_main0, hipEvent_t ev_main1) {
+                          hipEvent_t ev_main0, hipEvent_t ev_main1, bool dict) {
+    if (dict && (!A.btab || seg_bytes != 32768)) return hipErrorInvalidValue;
     // persistent grid: the workgroups that fit at once (CUs x workgroups per CU)
     int dev = 0, ncu = 0, per = 0;
     (void)hipGetDevice(&dev);
@@ -2141,7 +2185,10 @@ hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t 
     if (A.btab) {  // a batch: the same stages over the segment table, k_compact_batch at the end
         if (seg_bytes != 32768 && seg_bytes != 16384) return hipErrorInvalidValue;
         const bool l3 = A.level >= 3, s32 = seg_bytes == 32768;
-        if (grid && A.level >= 2) {
+        if (grid && A.level >= 2 && dict) {
+            if (l3) hipLaunchKernelGGL((k_deflate_segments<32768, true, true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+            else hipLaunchKernelGGL((k_deflate_segments<32768, false, true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+        } else if (grid && A.level >= 2) {
             if (s32 && l3) hipLaunchKernelGGL((k_deflate_segments<32768, true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
             else if (s32) hipLaunchKernelGGL((k_deflate_segments<32768, false, true>), dim3(grid), dim3(DF_NT), 0, st, A);
             else if (l3) hipLaunchKernelGGL((k_deflate_segments16<true, true>), dim3(grid), dim3(DF_NT), 0, st, A);

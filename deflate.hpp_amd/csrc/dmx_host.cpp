@@ -1280,14 +1280,24 @@ int inflate_device_async_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8
 // Batch deflate: one segment table over all buffers (DESIGN "Batched API"), uploaded with the
 // per-buffer arrays in one copy; one front launch, one emit launch, one scan and k_compact_batch
 // cover the batch, and the results come back in the call's only host synchronisation.
+// A preset dictionary (d_dict, dict_len > 0; 32 KiB segments): at levels 2 and 3 the first
+// segment of every buffer takes seg - Du bytes, Du = min(dict_len, kDeflateDictMax), and carries
+// the dictionary's last Du bytes (DeflateBatchSeg); the later segments are ordinary -- the
+// dictionary has left their window.  The segment count stays <= ceil(n / 16384), which
+// dmx_deflate_bound allows for.  Levels 0 and 1 have no matcher: their table is the plain one.
 int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count, int level,
-                         uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, hipStream_t st) {
+                         uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, hipStream_t st,
+                         const uint8_t* d_dict = nullptr, size_t dict_len = 0) {
     if (level < 0 || level > 3) level = 1;  // as deflate_device_locked
     const uint32_t seg = c->seg;
+    const uint32_t du = level >= 2 ? (uint32_t)std::min<size_t>(dict_len, kDeflateDictMax) : 0u;
+    if (du && seg != 32768) return DMX_ERR_ARG;
+    const uint8_t* const dtail = du ? d_dict + (dict_len - du) : nullptr;
+    const size_t seg0 = seg - du;  // bytes of a buffer's first segment
     uint64_t nseg = 0;
     for (size_t i = 0; i < count; i++) {
         if ((!d_in[i] && n[i]) || (!d_out[i] && cap[i])) return DMX_ERR_ARG;
-        nseg += (n[i] + seg - 1) / seg;
+        nseg += n[i] <= seg0 ? (n[i] ? 1 : 0) : 1 + (n[i] - seg0 + seg - 1) / seg;
     }
     // host image of the upload: segment table | first segment of each buffer | outputs | capacities
     const size_t off_first = nseg * sizeof(DeflateBatchSeg);
@@ -1298,19 +1308,21 @@ int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
     } catch (const std::bad_alloc&) {
         return DMX_ERR_NOMEM;
     }
-    static_assert(sizeof(DeflateBatchSeg) == 24 && sizeof(void*) == 8, "the upload image is built from 8-byte words");
+    static_assert(sizeof(DeflateBatchSeg) == 40 && sizeof(void*) == 8, "the upload image is built from 8-byte words");
     uint8_t* const img = reinterpret_cast<uint8_t*>(image.data());
     DeflateBatchSeg* tab = reinterpret_cast<DeflateBatchSeg*>(img);
     uint64_t* first = reinterpret_cast<uint64_t*>(img + off_first);
     uint64_t s = 0;
     for (size_t i = 0; i < count; i++) {
         first[i] = s;
-        for (size_t o = 0; o < n[i]; o += seg, s++) {
+        for (size_t o = 0, len = seg0; o < n[i]; o += len, len = seg, s++) {
             const size_t rest = n[i] - o;
             tab[s].src = d_in[i] + o;
             tab[s].tail = rest;
-            tab[s].nb = (uint32_t)std::min<size_t>(seg, rest);
-            tab[s].buf = (uint32_t)i | (rest <= seg ? DF_BATCH_LAST : 0u);
+            tab[s].nb = (uint32_t)std::min<size_t>(len, rest);
+            tab[s].buf = (uint32_t)i | (rest <= len ? DF_BATCH_LAST : 0u);
+            tab[s].dict = o == 0 ? dtail : nullptr;
+            tab[s].dlen = o == 0 ? du : 0u;
         }
         reinterpret_cast<uint64_t*>(img + off_out)[i] = (uint64_t)(uintptr_t)d_out[i];
         reinterpret_cast<uint64_t*>(img + off_cap)[i] = cap[i];
@@ -1351,7 +1363,7 @@ int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
     A.bcap = reinterpret_cast<const uint64_t*>(dimg + off_cap);
     A.bres = c->bres.as<dmx_batch_result>();
     A.nbuf = count;
-    HIPCHK(launch_deflate(A, seg, st, c->timing ? c->ev[1] : nullptr, c->timing ? c->ev[2] : nullptr));
+    HIPCHK(launch_deflate(A, seg, st, c->timing ? c->ev[1] : nullptr, c->timing ? c->ev[2] : nullptr, du != 0));
     HIPCHK(hipEventRecord(c->ev_df, st));
     c->df_pending = true;
     HIPCHK(hipMemcpyAsync(res, c->bres.p, count * sizeof(dmx_batch_result), hipMemcpyDeviceToHost, st));
@@ -1379,16 +1391,20 @@ constexpr size_t kBatchRouteBytes = 1u << 20;
 
 // Batch inflate: k_inflate_batch decodes the streams it keeps, longest first; the routed ones
 // follow through inflate_device_locked, one after another.
+// A preset dictionary (d_dict, dict_len > 0): the batch kernel pre-fills every stream's window
+// with its last min(dict_len, kInflateDictMax) bytes.  The single-stream plan knows no
+// dictionary, so no stream is routed then, whatever its size.
 int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count,
                          uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
-                         hipStream_t st) {
+                         hipStream_t st, const uint8_t* d_dict = nullptr, size_t dict_len = 0) {
     std::vector<uint32_t> order, routed;
     std::vector<uint64_t> image;
     const size_t off_order = count * sizeof(InflateBatchDesc);
+    const uint32_t dl = (uint32_t)std::min<size_t>(dict_len, kInflateDictMax);
     try {
         for (size_t i = 0; i < count; i++) {
             if ((!d_in[i] && n[i]) || (!d_out[i] && cap[i])) return DMX_ERR_ARG;
-            const bool route = !(flags & DMX_BATCH_NO_ROUTE) && n[i] > kBatchRouteBytes && d_out[i];
+            const bool route = !dl && !(flags & DMX_BATCH_NO_ROUTE) && n[i] > kBatchRouteBytes && d_out[i];
             (route ? routed : order).push_back((uint32_t)i);
         }
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return n[a] > n[b]; });
@@ -1408,10 +1424,15 @@ int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
     if (!c->btab.ensure(image.size() * 8) || !c->bres.ensure(res_bytes + 16)) return DMX_ERR_NOMEM;
     HIPCHK(hipMemcpyAsync(c->btab.p, img, image.size() * 8, hipMemcpyHostToDevice, st));
     if (c->timing) (void)hipEventRecord(c->ev[1], st);
-    HIPCHK(launch_inflate_batch(c->btab.as<InflateBatchDesc>(),
-                                reinterpret_cast<const uint32_t*>(c->btab.as<uint8_t>() + off_order), order.size(),
-                                c->bres.as<dmx_batch_result>(),
-                                reinterpret_cast<unsigned int*>(c->bres.as<uint8_t>() + res_bytes), c->flags, st));
+    const uint32_t* const d_order = reinterpret_cast<const uint32_t*>(c->btab.as<uint8_t>() + off_order);
+    unsigned int* const d_ticket = reinterpret_cast<unsigned int*>(c->bres.as<uint8_t>() + res_bytes);
+    if (dl)
+        HIPCHK(launch_inflate_batch_dict(c->btab.as<InflateBatchDesc>(), d_order, order.size(),
+                                         c->bres.as<dmx_batch_result>(), d_ticket, c->flags,
+                                         d_dict + (dict_len - dl), dl, st));
+    else
+        HIPCHK(launch_inflate_batch(c->btab.as<InflateBatchDesc>(), d_order, order.size(),
+                                    c->bres.as<dmx_batch_result>(), d_ticket, c->flags, st));
     if (c->timing) (void)hipEventRecord(c->ev[2], st);
     HIPCHK(hipEventRecord(c->ev_inf, st));
     c->inf_pending = true;
@@ -1873,39 +1894,58 @@ static bool batch_args_ok(const dmx_ctx* c, const void* in, const size_t* n, siz
     return c && count < (size_t)DF_BATCH_LAST && (count == 0 || (in && n && out && cap && res));
 }
 
-int dmx_deflate_batch_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count, int level,
-                             void* const* d_out, const size_t* cap, dmx_batch_result* res, void* stream) {
-    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res)) return DMX_ERR_ARG;
+// (the plain calls are the dictionary calls with dict_len == 0)
+int dmx_deflate_batch_dict_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count, int level,
+                                  const void* d_dict, size_t dict_len, void* const* d_out, const size_t* cap,
+                                  dmx_batch_result* res, void* stream) {
+    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res) || (dict_len && !d_dict)) return DMX_ERR_ARG;
     if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;  // 64 KiB blocks pair front segments
+    if (dict_len && c->seg != 32768) return DMX_ERR_ARG;  // the 16 KiB image has no room for one
     if (count == 0) return DMX_OK;
     std::lock_guard<std::mutex> g(c->mu);
     DeviceGuard dg(c->device);
     if (!dg.ok) return DMX_ERR_DEVICE;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return deflate_batch_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), n, count, level,
-                                reinterpret_cast<uint8_t* const*>(d_out), cap, res, st);
+                                reinterpret_cast<uint8_t* const*>(d_out), cap, res, st,
+                                static_cast<const uint8_t*>(d_dict), dict_len);
 }
 
-int dmx_inflate_batch_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count,
-                             void* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
-                             void* stream) {
-    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res) || (flags & ~DMX_BATCH_NO_ROUTE)) return DMX_ERR_ARG;
+int dmx_deflate_batch_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count, int level,
+                             void* const* d_out, const size_t* cap, dmx_batch_result* res, void* stream) {
+    return dmx_deflate_batch_dict_device(c, d_in, n, count, level, nullptr, 0, d_out, cap, res, stream);
+}
+
+int dmx_inflate_batch_dict_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count,
+                                  const void* d_dict, size_t dict_len, void* const* d_out, const size_t* cap,
+                                  dmx_batch_result* res, uint32_t flags, void* stream) {
+    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res) || (flags & ~DMX_BATCH_NO_ROUTE) || (dict_len && !d_dict))
+        return DMX_ERR_ARG;
     if (count == 0) return DMX_OK;
     std::lock_guard<std::mutex> g(c->mu);
     DeviceGuard dg(c->device);
     if (!dg.ok) return DMX_ERR_DEVICE;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return inflate_batch_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), n, count,
-                                reinterpret_cast<uint8_t* const*>(d_out), cap, res, flags, st);
+                                reinterpret_cast<uint8_t* const*>(d_out), cap, res, flags, st,
+                                static_cast<const uint8_t*>(d_dict), dict_len);
+}
+
+int dmx_inflate_batch_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count,
+                             void* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
+                             void* stream) {
+    return dmx_inflate_batch_dict_device(c, d_in, n, count, nullptr, 0, d_out, cap, res, flags, stream);
 }
 
 // Host buffers: the inputs are packed into one staging image at 16-byte aligned offsets and go up
 // in one copy; the outputs come back in one copy of the packed output area and are handed out.
-// ocap(i): the device bytes reserved for output i.
+// ocap(i): the device bytes reserved for output i.  A preset dictionary (dict_len > 0) follows the
+// inputs in the staging image and goes up in the same copy; run() gets its device address.
 extern "C++" {
 template <class OutCap, class Run>
 static int batch_host(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, uint8_t* const* out,
-                      const size_t* cap, dmx_batch_result* res, OutCap ocap, Run run) {
+                      const size_t* cap, dmx_batch_result* res, const uint8_t* dict, size_t dict_len, OutCap ocap,
+                      Run run) {
     for (size_t i = 0; i < count; i++)
         if ((!in[i] && n[i]) || (!out[i] && cap[i])) return DMX_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
@@ -1923,6 +1963,8 @@ static int batch_host(dmx_ctx* c, const uint8_t* const* in, const size_t* n, siz
         ti += (n[i] + 15) & ~size_t(15);
         to += (dcap[i] + 15) & ~size_t(15);
     }
+    const size_t doff = ti;
+    ti += (dict_len + 15) & ~size_t(15);
     try {
         stage.resize(std::max(ti, to));
     } catch (const std::bad_alloc&) {
@@ -1934,8 +1976,9 @@ static int batch_host(dmx_ctx* c, const uint8_t* const* in, const size_t* n, siz
         din[i] = c->in.as<uint8_t>() + ioff[i];
         dout[i] = c->out.as<uint8_t>() + ooff[i];
     }
+    if (dict_len) std::memcpy(stage.data() + doff, dict, dict_len);
     if (ti) HIPCHK(hipMemcpyAsync(c->in.p, stage.data(), ti, hipMemcpyHostToDevice, c->stream));
-    const int rc = run(din.data(), dout.data(), dcap.data());
+    const int rc = run(din.data(), dout.data(), dcap.data(), dict_len ? c->in.as<uint8_t>() + doff : nullptr);
     if (rc != DMX_OK) return rc;
     if (to) HIPCHK(hipMemcpyAsync(stage.data(), c->out.p, to, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1950,26 +1993,40 @@ static int batch_host(dmx_ctx* c, const uint8_t* const* in, const size_t* n, siz
 }
 }  // extern "C++"
 
+int dmx_deflate_batch_dict(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, int level,
+                           const uint8_t* dict, size_t dict_len, uint8_t* const* out, const size_t* cap,
+                           dmx_batch_result* res) {
+    if (!batch_args_ok(c, in, n, count, out, cap, res) || (dict_len && !dict)) return DMX_ERR_ARG;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;
+    if (dict_len && c->seg != 32768) return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    return batch_host(c, in, n, count, out, cap, res, dict, dict_len,
+                      [&](size_t i) { return std::min(cap[i], dmx_deflate_bound(n[i])); },
+                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc, const uint8_t* dd) {
+                          return deflate_batch_locked(c, di, n, count, level, dou, dc, res, c->stream, dd, dict_len);
+                      });
+}
+
 int dmx_deflate_batch(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, int level,
                       uint8_t* const* out, const size_t* cap, dmx_batch_result* res) {
-    if (!batch_args_ok(c, in, n, count, out, cap, res)) return DMX_ERR_ARG;
-    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;
+    return dmx_deflate_batch_dict(c, in, n, count, level, nullptr, 0, out, cap, res);
+}
+
+int dmx_inflate_batch_dict(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, const uint8_t* dict,
+                           size_t dict_len, uint8_t* const* out, const size_t* cap, dmx_batch_result* res,
+                           uint32_t flags) {
+    if (!batch_args_ok(c, in, n, count, out, cap, res) || (flags & ~DMX_BATCH_NO_ROUTE) || (dict_len && !dict))
+        return DMX_ERR_ARG;
     if (count == 0) return DMX_OK;
-    return batch_host(c, in, n, count, out, cap, res,
-                      [&](size_t i) { return std::min(cap[i], dmx_deflate_bound(n[i])); },
-                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc) {
-                          return deflate_batch_locked(c, di, n, count, level, dou, dc, res, c->stream);
+    return batch_host(c, in, n, count, out, cap, res, dict, dict_len, [&](size_t i) { return cap[i]; },
+                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc, const uint8_t* dd) {
+                          return inflate_batch_locked(c, di, n, count, dou, dc, res, flags, c->stream, dd, dict_len);
                       });
 }
 
 int dmx_inflate_batch(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, uint8_t* const* out,
                       const size_t* cap, dmx_batch_result* res, uint32_t flags) {
-    if (!batch_args_ok(c, in, n, count, out, cap, res) || (flags & ~DMX_BATCH_NO_ROUTE)) return DMX_ERR_ARG;
-    if (count == 0) return DMX_OK;
-    return batch_host(c, in, n, count, out, cap, res, [&](size_t i) { return cap[i]; },
-                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc) {
-                          return inflate_batch_locked(c, di, n, count, dou, dc, res, flags, c->stream);
-                      });
+    return dmx_inflate_batch_dict(c, in, n, count, nullptr, 0, out, cap, res, flags);
 }
 
 int dmx_deflate(dmx_ctx* c, const uint8_t* in, size_t n, int level, uint8_t* out, size_t cap,

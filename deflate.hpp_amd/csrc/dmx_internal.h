@@ -9,13 +9,21 @@ namespace dmx {
 
 // One segment of a batch: `nb` bytes at `src`; `tail` bytes are readable from src to the end of
 // its buffer (a word read may not run into a neighbour's allocation).
+// A preset dictionary (dmx_deflate_batch_dict_device): the first segment of every buffer carries
+// the last dlen <= kDeflateDictMax dictionary bytes at dict; the front kernel matches in the image
+// [dictionary bytes | the segment's nb bytes], dlen + nb <= the segment size, and emits tokens
+// for the segment's own bytes only.  dlen == 0: an ordinary segment.
 struct DeflateBatchSeg {
     const uint8_t* src;
     uint64_t tail;
     uint32_t nb;     // <= the context's segment size
     uint32_t buf;    // buffer index | DF_BATCH_LAST on the last segment of its buffer (BFINAL)
+    const uint8_t* dict;
+    uint64_t dlen;
 };
 constexpr uint32_t DF_BATCH_LAST = 1u << 31;
+constexpr uint32_t kDeflateDictMax = 16384;  // dictionary bytes the deflate side uses (the last ones)
+constexpr uint32_t kInflateDictMax = 32768;  // ... and the inflate side: the DEFLATE window
 
 struct DeflateArgs {
     const uint8_t* in;
@@ -52,8 +60,9 @@ struct DeflateArgs {
 constexpr uint32_t kDeflateHistWords = 160;
 constexpr uint32_t deflate_tok_stride(uint32_t seg) { return seg / 2 + 1024 + 64 + kDeflateHistWords; }
 
+// dict: the batch's segment table carries a preset dictionary (32 KiB segments, levels 2-3)
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, hipEvent_t ev0,
-                          hipEvent_t ev1);
+                          hipEvent_t ev1, bool dict = false);
 
 // per-candidate record of the segment-parallel inflate
 struct SegRecord {
@@ -274,6 +283,9 @@ hipError_t launch_inflate_serial(const InflateArgs& A, int count_only, InflateRe
 // batch inflate (inflate_batch.hip): one wavefront per stream on a persistent grid.  order
 // lists the norder streams to decode (indices into desc / res), longest first; workgroups draw
 // positions of it from *ticket (zeroed by the launch).  flags: DMX_CFG_RFC_STRICT.
+// launch_inflate_batch_dict: dict holds the preset dictionary's last dl bytes, 0 < dl <=
+// kInflateDictMax (device memory, any alignment), which every stream's window holds before its
+// first byte.
 struct InflateBatchDesc {
     const uint8_t* in;
     uint64_t n;
@@ -282,5 +294,8 @@ struct InflateBatchDesc {
 };
 hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
                                 ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st);
+hipError_t launch_inflate_batch_dict(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
+                                     ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags,
+                                     const uint8_t* dict, uint32_t dl, hipStream_t st);
 
 }  // namespace dmx

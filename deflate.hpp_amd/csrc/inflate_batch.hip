@@ -31,7 +31,23 @@ using BatchIn = RingInT<BT_RW, BT_RC>;
 // of the same wave-wide store, which executes after the wave-wide load.
 // Bytes past `cap` are counted, not written; a distance beyond the stream start copies nothing,
 // as in the reference (inflate.hpp:268-270).
-struct BatchSink {
+// A preset dictionary (dmx_inflate_batch_dict_device) is history before byte 0: the wave fills
+// the ring with its last dl <= 32768 bytes before decoding (batch_prefill), dictionary byte j at
+// slot (j - dl) mod 32768, i.e. where output byte j - dl would lie.  pos still starts at 0 and
+// the invariant above is unchanged -- the slots behind pos hold real history instead of stale
+// bytes -- and the stream start moves back by dl: only a distance beyond pos + dl copies nothing.
+// The dictionary itself is never flushed (flushed starts at 0, like pos).
+template <bool DICT>
+struct BatchHistory {  // DICT: dictionary bytes in the ring before byte 0
+    uint32_t dl;
+    __device__ uint32_t before() const { return dl; }
+};
+template <>
+struct BatchHistory<false> {  // (the plain sink carries no such member)
+    __device__ uint32_t before() const { return 0; }
+};
+template <bool DICT>
+struct BatchSink : BatchHistory<DICT> {
     uint8_t* ring;     // BT_RING bytes of LDS
     uint64_t pos;      // output bytes so far
     uint64_t flushed;  // bytes [0, min(flushed, cap)) are in `out`
@@ -56,10 +72,10 @@ struct BatchSink {
     }
     __device__ bool copy(uint32_t L, uint32_t dist) {
         if (L == 0 || dist == 0) return true;
-        if (dist > pos) return true;  // reference: nothing to copy (inflate.hpp:268-270)
+        if (dist > pos + this->before()) return true;  // reference: nothing to copy (inflate.hpp:268-270)
         wave_sync();
         const uint32_t lane = lane_id();
-        const uint64_t src = pos - dist;
+        const uint64_t src = pos - dist;  // (before byte 0: wraps, and 2^64 is a multiple of the ring)
         if (dist >= L || dist >= 64) {  // each group of 64 reads only bytes written before it
             for (uint32_t i = lane; i < L; i += 64) {
                 ring[(pos + i) & (BT_RING - 1)] = ring[(src + i) & (BT_RING - 1)];
@@ -92,9 +108,31 @@ struct BatchSink {
     }
 };
 
+// the dictionary's dl bytes into the ring slots [32768 - dl, 32768): 16 B per lane where the
+// source allows it (ring slot and source address congruent mod 16), bytes at the ends
+__device__ __forceinline__ void batch_prefill(uint8_t* ring, const uint8_t* dict, uint32_t dl) {
+    const uint32_t lane = lane_id();
+    uint8_t* const dst = ring + (BT_RING - dl);
+    uint32_t head = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(dict) & 15)) & 15u;
+    if (((BT_RING - dl + head) & 15u) != 0 || head > dl) head = dl;  // not congruent: bytes throughout
+    for (uint32_t i = lane; i < head; i += 64) dst[i] = dict[i];
+    const uint32_t nvec = (dl - head) / 16;
+    const uint4* const s4 = reinterpret_cast<const uint4*>(dict + head);
+    uint4* const d4 = reinterpret_cast<uint4*>(dst + head);
+    for (uint32_t i = lane; i < nvec; i += 64) d4[i] = s4[i];
+    for (uint32_t i = head + 16 * nvec + lane; i < dl; i += 64) dst[i] = dict[i];
+}
+
+// DICT: the streams were made with a preset dictionary (dict / dl, 0 < dl <= 32768).  Each
+// instantiation is compiled in a translation unit of its own (inflate_batch_dict.hip includes
+// this file with DMX_BATCH_DICT set): with both in one unit the decoder's helper functions have
+// two callers, are no longer inlined, and the plain kernel goes from 123 VGPRs and no scratch
+// to 162 VGPRs and 12 bytes of scratch.
+template <bool DICT>
 __global__ __launch_bounds__(IF_NT) void k_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order,
                                                          uint64_t norder, ::dmx_batch_result* res,
-                                                         unsigned int* ticket, uint32_t flags) {
+                                                         unsigned int* ticket, uint32_t flags,
+                                                         const uint8_t* dict, uint32_t dl) {
     __shared__ __attribute__((aligned(16))) uint8_t ring[BT_RING];
     __shared__ uint32_t inring[BT_RW];
     __shared__ Tables T;
@@ -116,7 +154,11 @@ __global__ __launch_bounds__(IF_NT) void k_inflate_batch(const InflateBatchDesc*
             BatchIn br;
             br.init(reinterpret_cast<const uint32_t*>(d.in - misalign), misalign, d.n, inring);
             br.seek(misalign * 8);
-            BatchSink sk{ring, 0, 0, d.out, d.cap, 0};
+            BatchSink<DICT> sk{{}, ring, 0, 0, d.out, d.cap, 0};
+            if constexpr (DICT) {
+                sk.dl = dl;
+                batch_prefill(ring, dict, dl);  // (copy()'s wave_sync orders it before the reads)
+            }
             uint64_t end_byte = 0;
             bool fin = false;
             const uint32_t err = inflate_blocks(br, T, sk, (flags & DMX_CFG_RFC_STRICT) != 0, false, &end_byte, &fin);
@@ -133,18 +175,32 @@ __global__ __launch_bounds__(IF_NT) void k_inflate_batch(const InflateBatchDesc*
     }
 }
 
+#ifndef DMX_BATCH_DICT
+#define DMX_BATCH_DICT 0
+#endif
+#if DMX_BATCH_DICT
+hipError_t launch_inflate_batch_dict(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
+                                     ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags,
+                                     const uint8_t* dict, uint32_t dl, hipStream_t st) {
+    if (!dict || dl == 0 || dl > kInflateDictMax) return hipErrorInvalidValue;
+#else
 hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
                                 ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st) {
+    const uint8_t* const dict = nullptr;
+    const uint32_t dl = 0;
+#endif
+    constexpr bool DICT = DMX_BATCH_DICT != 0;
     if (!norder) return hipSuccess;
     int dev = 0, ncu = 0, per = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_inflate_batch, IF_NT, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_inflate_batch<DICT>, IF_NT, 0);
     const uint64_t fit = (uint64_t)max(ncu, 1) * (uint64_t)max(per, 1);
     const uint32_t grid = (uint32_t)(norder < fit ? norder : fit);
     const hipError_t e = hipMemsetAsync(ticket, 0, sizeof(unsigned int), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_inflate_batch, dim3(grid), dim3(IF_NT), 0, st, desc, order, norder, res, ticket, flags);
+    hipLaunchKernelGGL(k_inflate_batch<DICT>, dim3(grid), dim3(IF_NT), 0, st, desc, order, norder, res, ticket, flags,
+                       dict, dl);
     return hipGetLastError();
 }
 

@@ -40,7 +40,8 @@ EXPORTS = [
     "dmx_deflate_file", "dmx_inflate_file", "dmx_segment_starts_device", "dmx_inflate_piece_device",
     "dmx_segment_check_device", "dmx_set_default_config", "dmx_deflate_device_async",
     "dmx_inflate_device_async", "dmx_deflate_batch_device", "dmx_inflate_batch_device",
-    "dmx_deflate_batch", "dmx_inflate_batch",
+    "dmx_deflate_batch", "dmx_inflate_batch", "dmx_deflate_batch_dict_device",
+    "dmx_inflate_batch_dict_device", "dmx_deflate_batch_dict", "dmx_inflate_batch_dict",
 ]
 
 
@@ -129,6 +130,10 @@ def lib():
     L.dmx_inflate_batch_device.argtypes = [vp, vp, vp, sz, vp, vp, brp, ctypes.c_uint32, vp]
     L.dmx_deflate_batch.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp, vp, brp]
     L.dmx_inflate_batch.argtypes = [vp, vp, vp, sz, vp, vp, brp, ctypes.c_uint32]
+    L.dmx_deflate_batch_dict_device.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp, sz, vp, vp, brp, vp]
+    L.dmx_inflate_batch_dict_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, brp, ctypes.c_uint32, vp]
+    L.dmx_deflate_batch_dict.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp, sz, vp, vp, brp]
+    L.dmx_inflate_batch_dict.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, brp, ctypes.c_uint32]
     _lib = L
     return L
 
@@ -390,21 +395,35 @@ class Context:
         return (k, (ctypes.c_void_p * m)(*ptrs), (ctypes.c_size_t * m)(*sizes), (ctypes.c_void_p * m)(*out_ptrs),
                 (ctypes.c_size_t * m)(*caps), (BatchResult * m)())
 
-    def deflate_batch_device(self, ptrs, sizes, level, out_ptrs, caps, stream=None):
+    def deflate_batch_device(self, ptrs, sizes, level, out_ptrs, caps, stream=None, dict_ptr=None, dict_len=0):
         """dmx_deflate_batch_device: device pointers / sizes per buffer -> [(bytes, status, path)].
-        Buffer i gets exactly the stream deflate_device writes for it alone."""
+        Buffer i gets exactly the stream deflate_device writes for it alone.  dict_ptr / dict_len:
+        a preset dictionary in device memory (dmx_deflate_batch_dict_device); the streams then
+        decode with zlib.decompressobj(-15, zdict=...)."""
         k, a_in, a_n, a_out, a_cap, res = self._batch_arrays(ptrs, sizes, out_ptrs, caps)
-        _check(lib().dmx_deflate_batch_device(self.h, a_in, a_n, k, level, a_out, a_cap, res,
-                                              ctypes.c_void_p(stream) if stream else None), "deflate_batch_device")
+        sp = ctypes.c_void_p(stream) if stream else None
+        if dict_ptr is None and not dict_len:
+            _check(lib().dmx_deflate_batch_device(self.h, a_in, a_n, k, level, a_out, a_cap, res, sp),
+                   "deflate_batch_device")
+        else:
+            _check(lib().dmx_deflate_batch_dict_device(self.h, a_in, a_n, k, level, ctypes.c_void_p(dict_ptr),
+                                                       dict_len, a_out, a_cap, res, sp), "deflate_batch_dict_device")
         return [(r.bytes, r.status, r.path) for r in res[:k]]
 
-    def inflate_batch_device(self, ptrs, sizes, out_ptrs, caps, stream=None, no_route=False):
+    def inflate_batch_device(self, ptrs, sizes, out_ptrs, caps, stream=None, no_route=False, dict_ptr=None,
+                             dict_len=0):
         """dmx_inflate_batch_device -> [(bytes, status, path)]; no_route: every stream on the
-        batch decoder, however long (developer A/B)."""
+        batch decoder, however long (developer A/B).  dict_ptr / dict_len: the preset dictionary
+        the streams were made with, in device memory (dmx_inflate_batch_dict_device)."""
         k, a_in, a_n, a_out, a_cap, res = self._batch_arrays(ptrs, sizes, out_ptrs, caps)
-        _check(lib().dmx_inflate_batch_device(self.h, a_in, a_n, k, a_out, a_cap, res,
-                                              DMX_BATCH_NO_ROUTE if no_route else 0,
-                                              ctypes.c_void_p(stream) if stream else None), "inflate_batch_device")
+        fl = DMX_BATCH_NO_ROUTE if no_route else 0
+        sp = ctypes.c_void_p(stream) if stream else None
+        if dict_ptr is None and not dict_len:
+            _check(lib().dmx_inflate_batch_device(self.h, a_in, a_n, k, a_out, a_cap, res, fl, sp),
+                   "inflate_batch_device")
+        else:
+            _check(lib().dmx_inflate_batch_dict_device(self.h, a_in, a_n, k, ctypes.c_void_p(dict_ptr), dict_len,
+                                                       a_out, a_cap, res, fl, sp), "inflate_batch_dict_device")
         return [(r.bytes, r.status, r.path) for r in res[:k]]
 
     def _batch_host(self, fn, datas, caps, mid=(), tail=()):
@@ -418,20 +437,32 @@ class Context:
         _check(getattr(lib(), fn)(*args), fn)
         return outs, res[:k]
 
-    def compress_batch(self, datas, level=2):
-        """Raw DEFLATE stream of every buffer in one call: equal to [compress(d, level) ...]."""
-        outs, res = self._batch_host("dmx_deflate_batch", datas, [deflate_bound(len(d)) for d in datas], mid=(level,))
+    def compress_batch(self, datas, level=2, zdict=None):
+        """Raw DEFLATE stream of every buffer in one call: equal to [compress(d, level) ...].
+        zdict: a preset dictionary shared by all buffers, as zlib.compressobj's zdict."""
+        caps = [deflate_bound(len(d)) for d in datas]
+        if zdict is None:
+            outs, res = self._batch_host("dmx_deflate_batch", datas, caps, mid=(level,))
+        else:
+            zdict = bytes(zdict)
+            outs, res = self._batch_host("dmx_deflate_batch_dict", datas, caps, mid=(level, zdict, len(zdict)))
         for r in res:
             _check(r.status, "deflate_batch")
         return [o.raw[: r.bytes] for o, r in zip(outs, res)]
 
-    def decompress_batch(self, datas, caps, no_route=False, with_results=False):
+    def decompress_batch(self, datas, caps, zdict=None, no_route=False, with_results=False):
         """Inflate every stream in one call.  caps[i] bounds output i; each element is the
         decoded bytes, or the DmxError that decompress would raise for that stream alone
-        (DMX_ERR_CAPACITY when it needs more than caps[i]).  with_results: also the list of
+        (DMX_ERR_CAPACITY when it needs more than caps[i]).  zdict: the preset dictionary the
+        streams were made with, as zlib.decompressobj's zdict.  with_results: also the list of
         (bytes, status, path) per stream."""
-        outs, res = self._batch_host("dmx_inflate_batch", datas, list(caps),
-                                     tail=(DMX_BATCH_NO_ROUTE if no_route else 0,))
+        fl = DMX_BATCH_NO_ROUTE if no_route else 0
+        if zdict is None:
+            outs, res = self._batch_host("dmx_inflate_batch", datas, list(caps), tail=(fl,))
+        else:
+            zdict = bytes(zdict)
+            outs, res = self._batch_host("dmx_inflate_batch_dict", datas, list(caps), mid=(zdict, len(zdict)),
+                                         tail=(fl,))
         vals = [o.raw[: r.bytes] if r.status == DMX_OK else DmxError(r.status, "inflate_batch")
                 for o, r in zip(outs, res)]
         return (vals, [(r.bytes, r.status, r.path) for r in res]) if with_results else vals

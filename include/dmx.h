@@ -251,6 +251,48 @@ int dmx_deflate_batch(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, s
 int dmx_inflate_batch(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, size_t count,
                       uint8_t* const* out, const size_t* cap, dmx_batch_result* res, uint32_t flags);
 
+/* ---- preset dictionary for the batched calls (zlib's deflateSetDictionary /
+ * inflateSetDictionary on raw RFC 1951 streams; not in the reference) -------------------------
+ * Small buffers start with an empty window; a dictionary of typical content gives every buffer of
+ * the batch history to refer to.  One dictionary per call, shared by all its buffers.  Semantics
+ * are zlib's: a stream made with dictionary d decodes exactly when the decoder's window holds the
+ * last <= 32768 bytes of d before the stream's first output byte -- libdmx's streams decode with
+ * zlib.decompressobj(-15, zdict=d), and zlib's compressobj(level, DEFLATED, -15, zdict=d) streams
+ * decode here given d.  No framing carries the dictionary: both sides must be given the same one.
+ *
+ * dict_len == 0 (a null dictionary is allowed then) is the plain batch call, byte for byte and
+ * result for result.  dict_len > 0 with a null dictionary is DMX_ERR_ARG.  Return value and
+ * res[i] follow the rules of the batch calls above.
+ *
+ * Deflate uses the last min(dict_len, 16384) bytes (Du) at levels 2 and 3: the first segment of a
+ * buffer then holds 32768 - Du of its bytes (the dictionary shares the matcher's 32 KiB image),
+ * the later segments are ordinary, and dmx_deflate_bound(n[i]) still bounds the stream.  Levels 0
+ * and 1 have no matcher and ignore the dictionary; their streams are the plain ones and decode
+ * with or without it.  Only contexts with segment_bytes = 32768 take a dictionary: any other
+ * returns DMX_ERR_ARG when dict_len > 0.
+ *
+ * Inflate uses the last min(dict_len, 32768) bytes, with any context.  A distance that reaches
+ * before the dictionary copies nothing (the stream-start rule of dmx_inflate, moved back by the
+ * dictionary).  With dict_len > 0 every stream is decoded by the batch decoder (path 6) whatever
+ * its size -- the single-stream plan has no dictionary support -- and DMX_BATCH_NO_ROUTE is
+ * accepted and changes nothing.  A wrong dictionary is not detected: the stream decodes to other
+ * bytes or ends in DMX_ERR_DATA, as with zlib's raw streams.
+ *
+ * d_dict: a device pointer with any alignment.  The host forms stage the dictionary with the
+ * batch's one H2D copy. */
+int dmx_deflate_batch_dict_device(dmx_ctx* ctx, const void* const* d_in, const size_t* n, size_t count,
+                                  int level, const void* d_dict, size_t dict_len, void* const* d_out,
+                                  const size_t* cap, dmx_batch_result* res, void* stream);
+int dmx_inflate_batch_dict_device(dmx_ctx* ctx, const void* const* d_in, const size_t* n, size_t count,
+                                  const void* d_dict, size_t dict_len, void* const* d_out,
+                                  const size_t* cap, dmx_batch_result* res, uint32_t flags, void* stream);
+int dmx_deflate_batch_dict(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, size_t count, int level,
+                           const uint8_t* dict, size_t dict_len, uint8_t* const* out, const size_t* cap,
+                           dmx_batch_result* res);
+int dmx_inflate_batch_dict(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, size_t count,
+                           const uint8_t* dict, size_t dict_len, uint8_t* const* out, const size_t* cap,
+                           dmx_batch_result* res, uint32_t flags);
+
 /* ---- checksums and containers (not in the reference) -------------------
  * The reference's decompressZlib (inflate.hpp:326-361) skips the 2-byte header and ignores the
  * Adler-32 (SURVEY A-9); inflate.hpp's decompressZlib keeps exactly that.  These entry points
@@ -275,7 +317,8 @@ int dmx_deflate_gzip(dmx_ctx* ctx, const uint8_t* in, size_t n, int level, uint8
 
 /* Check the container trailer against the decoded bytes (DMX_ERR_CHECKSUM on mismatch). */
 #define DMX_VERIFY 1u
-/* Inflate of a zlib stream (header checked; preset dictionaries are DMX_ERR_DATA) / a
+/* Inflate of a zlib stream (header checked; a container with FDICT set is DMX_ERR_DATA -- the
+ * preset-dictionary calls dmx_inflate_batch_dict* take raw streams, not this framing) / a
  * single-member gzip stream (FEXTRA, FNAME, FCOMMENT, FHCRC skipped); the trailer is the last
  * 4 / 8 input bytes.  *out is allocated by the library (dmx_free). */
 int dmx_inflate_zlib(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t** out, size_t* len);

@@ -7,15 +7,21 @@ profiles/batch_probe.json, which DESIGN quotes.
 2. routing crossover: single libdmx level-2 text streams of 64 KiB .. 16 MiB,
    inflate_batch_device(no_route=True) against inflate_device.
 
+3. preset dictionary (--dict, writes profiles/batch_probe_dict.json): 16384 x 1 KiB and
+   16384 x 4 KiB pages of synthetic JSON log records, level 2, an 8 KiB dictionary of other
+   records of the same generator; the batch calls with the dictionary against the same calls
+   without it, alternated; ms per call and total compressed bytes of both.
+
 Timing: synchronised host wall clock around each call (every call ends in a host
 synchronisation of its own), WARM warm-up repetitions, then REPS measured ones; the median is
 reported with the minimum beside it.
 
-  python tools/batch_probe.py [--reps 20] [--quick]
+  python tools/batch_probe.py [--reps 20] [--quick] [--dict]
 """
 import argparse
 import json
 import os
+import random
 import statistics
 import sys
 import time
@@ -109,16 +115,90 @@ def crossover(ctx, size, reps):
             "batch_kernel_wins": statistics.median(tb) < statistics.median(ts)}
 
 
+HOSTS = ["gpu-node-%02d.cluster.example" % i for i in range(12)]
+LEVELS = ["INFO", "WARN", "ERROR", "DEBUG"]
+MSGS = ["kernel launch completed", "allocation of device buffer failed", "segment table uploaded",
+        "stream synchronised", "checksum verified", "window hand-off finished"]
+
+
+def records(seed, nbytes):
+    """Deterministic JSON-ish log lines (the generator of tests/test_gpu_dict.py)."""
+    r = random.Random(seed)
+    out = bytearray()
+    while len(out) < nbytes:
+        out += ('{"timestamp":"2026-10-%02dT%02d:%02d:%02dZ","host":"%s","level":"%s","message":"%s",'
+                '"bytes":%d,"latency_us":%d}\n' % (
+                    r.randrange(1, 29), r.randrange(24), r.randrange(60), r.randrange(60), r.choice(HOSTS),
+                    r.choice(LEVELS), r.choice(MSGS), r.randrange(1 << 20), r.randrange(100000))).encode()
+    return bytes(out[:nbytes])
+
+
+def dict_vs_plain(ctx, count, size, reps, dict_bytes=8192):
+    d = records(1, dict_bytes)
+    data = records(100, count * size)
+    d_d = torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda()
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    bound = (dmx.deflate_bound(size) + 15) & ~15
+    d_c = [torch.empty(count * bound, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    d_o = torch.empty(count * size, dtype=torch.uint8, device="cuda")
+    ins = [d_in.data_ptr() + i * size for i in range(count)]
+    comps = [[t.data_ptr() + i * bound for i in range(count)] for t in d_c]
+    outs = [d_o.data_ptr() + i * size for i in range(count)]
+    sizes, bounds = [size] * count, [bound] * count
+    clen = [[], []]
+    kw = [{}, {"dict_ptr": d_d.data_ptr(), "dict_len": len(d)}]
+
+    def deflate(k):
+        def run():
+            res = ctx.deflate_batch_device(ins, sizes, 2, comps[k], bounds, **kw[k])
+            assert all(r[1] == dmx.DMX_OK for r in res)
+            clen[k][:] = [r[0] for r in res]
+        return run
+
+    def inflate(k):
+        def run():
+            d_o.zero_()
+            res = ctx.inflate_batch_device(comps[k], clen[k], outs, sizes, **kw[k])
+            assert all(r[1:] == (dmx.DMX_OK, dmx.BATCH_PATH) for r in res)
+        return run
+
+    dp, dd = alternate(deflate(0), deflate(1), reps)
+    ip, id_ = alternate(inflate(0), inflate(1), reps)
+    assert d_o.cpu().numpy().tobytes() == data, "round trip mismatch (with dictionary)"
+    inflate(0)()
+    assert d_o.cpu().numpy().tobytes() == data, "round trip mismatch (without)"
+    return {"kind": "records", "count": count, "size": size, "dict_bytes": len(d), "level": 2,
+            "compressed_bytes_plain": sum(clen[0]), "compressed_bytes_dict": sum(clen[1]),
+            "bytes_dict_over_plain": sum(clen[1]) / sum(clen[0]),
+            "deflate_plain": summary(dp), "deflate_dict": summary(dd),
+            "inflate_plain": summary(ip), "inflate_dict": summary(id_)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="an eighth of the buffer counts (a check of the tool)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_probe.json"))
+    ap.add_argument("--dict", action="store_true", help="only the preset-dictionary shapes (part 3)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "batch_probe_dict.json" if a.dict else "batch_probe.json")
     if not torch.cuda.is_available():
         sys.exit("batch_probe: no GPU")
     ctx = dmx.Context()
     q = 8 if a.quick else 1
+    if a.dict:
+        result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
+                  "timing": "synchronised host wall clock per call, with and without dictionary alternated",
+                  "dict_vs_plain": []}
+        for size in (1024, 4096):
+            row = dict_vs_plain(ctx, 16384 // q, size, a.reps)
+            result["dict_vs_plain"].append(row)
+            print(json.dumps(row), flush=True)
+            with open(a.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+        ctx.close()
+        return
     result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
               "timing": "synchronised host wall clock per call, batch and loop alternated",
               "batch_vs_loop": [], "routing_crossover": []}
