@@ -1,0 +1,158 @@
+// dmx_ctx.h -- the context and the small pieces the host translation units share (dmx_host.cpp:
+// context, deflate, batch, containers, files, multi-GPU, C-ABI; host_inflate.cpp: the segmented
+// inflate plan, the async path, the serial fallback; host_fb.cpp: path 5).
+//
+// A context owns one HIP device, one non-blocking stream and grow-only device scratch
+// (segment slots, size/offset arrays, candidate lists, look-back words).  Every entry point
+// locks the context, so a context may be shared between threads; the default context is
+// created once per process (std::call_once) on the caller's current device.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/dmx.h"
+#include "dmx_internal.h"
+
+namespace dmx {
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    bool ensure(size_t bytes) {
+        if (bytes <= cap) return true;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        size_t want = bytes + bytes / 8 + 4096;
+        if (hipMalloc(&p, want) != hipSuccess) {
+            p = nullptr;
+            return false;
+        }
+        cap = want;
+        return true;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+}  // namespace dmx
+
+struct dmx_ctx {
+    using DevBuf = dmx::DevBuf;
+    int device = 0;
+    uint32_t seg = 32768;
+    uint32_t flags = 0;
+    int inflate_pass = -1;     // dmx_config.dev_inflate_pass - 1: forced pass, -1 = the plan
+    uint32_t heavy_bytes = 0;  // dmx_config.dev_heavy_bytes
+    uint32_t diag = 0;         // DIAG_* bits, read once from the environment at dmx_create
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    DevBuf in, out, slots, sizes, offs, scal, cands, tiles, tileoffs, recs, status, dbg;
+    DevBuf dtok, dntok;                  // deflate: the front kernel's token words and counts
+    DevBuf rtmp, rchain;                 // chain repair: scratch output, chain / offsets / sizes
+    DevBuf ltok, ltokoff, lntok, lcaps, lsplit;  // lane decoder token lists (mode 4), 64 KiB halves
+    DevBuf lheavy;                       // heavy-candidate list for the workgroup decoder (mode 6)
+    int ncu = 256;                       // compute units, read at dmx_create (mode 6 grid, lane resolve)
+    // block-parallel path (path 5): scan counts / hits / offsets, hit list, unit starts, token
+    // offsets and words, unit records, chain (unit index, offset, size), 16-bit image
+    DevBuf fbc, fbh, fbo, fbl, fbs, fbt, fbk, fbu, fbch, fbco, fbcs, fbimg, fbstop, fbwin, fbopen;
+    DevBuf fbvm, fbvh;  // per-unit start mode and code state (region and repair units)
+    DevBuf fbph;  // DMX_FB_DEBUG: k_fb_units phase cycles
+    // path 5: the accepted unit starts, written by k_fb_check straight into host memory
+    uint64_t* fbkeep_h = nullptr;
+    uint64_t* fbkeep_d = nullptr;
+    // path 5: pinned staging of host-to-device uploads (a copy from pageable memory goes through
+    // the driver's own staging); reused per batch -- a stream sync separates the batches
+    uint8_t* pin = nullptr;
+    size_t pin_cap = 0, pin_off = 0;
+    DevBuf fbreg, fbJ, fbvis;  // fixed-code regions: {E, T, first super block} + super-block regions, jumps, visits
+    DevBuf fbJraw, fbJsub, fbcbit, fbucb;  // regions: chunk maps, sub-chunk entries, chunk entries, unit chunk
+    DevBuf ck;  // checksum scratch (checksum.hip) + the 4-byte result at its start
+    DevBuf btab, bres;  // batch calls: the uploaded tables / descriptors; the results + the ticket
+    bool timing = false;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_df = nullptr;          // end of the last deflate's work (its scratch is reused)
+    hipEvent_t ev_inf = nullptr;         // end of the last asynchronous inflate's work
+    bool inf_pending = false;
+    bool df_pending = false;
+    dmx_stats stats{};
+    uint64_t last_end = 0;               // the last inflate: stream byte just past its final block
+    std::vector<dmx_ctx*> subs;          // n_gpus > 1: one context per shard / piece
+};
+
+namespace dmx {
+
+// Diagnostics (never steer results): read from the environment once, at dmx_create.
+//   DMX_DEBUG=1       names the failing HIP call on stderr (process-wide)
+//   DMX_PHASES=<file> per-phase s_memtime timelines of the segmented kernels
+//   DMX_FB_DEBUG=1    block-parallel path: unit outcomes and chain breaks on stderr
+//   DMX_FB_HOSTTIME=1 block-parallel path: host wall clock per phase on stderr
+//   DMX_RECS=1        segmented inflate: per-candidate outcome of each pass on stderr
+enum : uint32_t { DIAG_PHASES = 1, DIAG_FB = 2, DIAG_RECS = 4, DIAG_DEBUG = 8, DIAG_FBT = 16 };
+struct Diag {
+    uint32_t bits = 0;
+    std::string phases_path;
+};
+const Diag& diag_env();  // first use (a dmx_create) reads the environment
+void hipchk_report(const char* what, hipError_t e, const char* file, int line);
+#define HIPCHK(x)                                          \
+    do {                                                   \
+        const hipError_t e_ = (x);                         \
+        if (e_ != hipSuccess) {                            \
+            hipchk_report(#x, e_, __FILE_NAME__, __LINE__); \
+            return DMX_ERR_DEVICE;                         \
+        }                                                  \
+    } while (0)
+
+struct Scal {  // small device-side scalars, one allocation
+    uint64_t total;
+    uint64_t nmarkers;
+    uint32_t ticket;
+    uint32_t fb_err;  // block-parallel path: a copy reached before the stream start
+    uint32_t fb_nkeep;  // block-parallel path: accepted unit starts (k_fb_check)
+    uint64_t ncand;     // dmx_inflate_device_async: the candidate count, on the device
+    InflateResult res;
+    ValidateWords vw;
+};
+
+// DMX_PHASES=<file>: kernels record s_memtime per phase and segment; the host appends one line
+// "<kernel> <nsegs> <mean cycles of phase k - phase k-1 ...>" per call (developer profiling).
+uint64_t* phase_buf(dmx_ctx* c, uint64_t nidx);
+void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st);
+
+void begin_timing(dmx_ctx* c, hipStream_t st);
+void end_timing(dmx_ctx* c, hipStream_t st);
+
+// the stream seen as aligned words (the kernels read 4-byte words at or below its start)
+struct StreamWords {
+    const uint32_t* words;
+    uint64_t misalign;
+    explicit StreamWords(const uint8_t* d_in)
+        : words(reinterpret_cast<const uint32_t*>(d_in - ((uintptr_t)d_in & 3))), misalign((uintptr_t)d_in & 3) {}
+};
+
+// host_inflate.cpp
+// candidate segment starts: counts the markers per tile and scans the counts (Scal::nmarkers
+// receives the total, nothing waits); then marker_write lists bit 0 and the markers in c->cands
+int marker_scan(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t* ntiles, hipStream_t st);
+int marker_write(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t ntiles, uint64_t cand_cap, hipStream_t st);
+// Shared inflate driver.  fixed_out != nullptr: decode into the caller's device buffer of
+// `cap` bytes.  Otherwise decode into c->out, grown as needed (*dev_out receives it).
+// iflags: DMX_IFLAG_PIECE for one piece of a larger stream (dmx_inflate_piece_device).
+int inflate_device_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8_t* fixed_out, size_t cap,
+                          size_t* total_out, uint8_t** dev_out, hipStream_t st, uint32_t iflags = 0);
+int inflate_device_async_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap,
+                                uint64_t* d_result, hipStream_t st, uint32_t iflags);
+// host_fb.cpp
+int inflate_fb_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8_t* fixed_out, size_t cap,
+                      size_t* total_out, uint8_t** dev_out, hipStream_t st, bool* handled, uint32_t iflags);
+
+}  // namespace dmx

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/dmx.h"
+#include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
 
 namespace dmx {
 
@@ -63,24 +64,6 @@ constexpr uint32_t deflate_tok_stride(uint32_t seg) { return seg / 2 + 1024 + 64
 // dict: the batch's segment table carries a preset dictionary (32 KiB segments, levels 2-3)
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, hipEvent_t ev0,
                           hipEvent_t ev1, bool dict = false);
-
-// per-candidate record of the segment-parallel inflate
-struct SegRecord {
-    uint64_t end_byte;  // byte offset (relative to the stream) just past the segment's marker
-    uint64_t offset;    // output offset the segment was written at
-    uint32_t out_size;
-    uint32_t flags;     // SEGF_*
-};
-enum : uint32_t {
-    SEGF_FINAL = 1u,      // the segment ended with a BFINAL block
-    SEGF_ERR_DATA = 2u,   // undecodable code / table
-    SEGF_OVERREAD = 4u,   // ran past the end of the input
-    SEGF_OVERFLOW = 8u,   // output exceeded the LDS window
-    SEGF_XREF = 16u,      // back-reference reaches before the segment start
-    SEGF_TIMEOUT = 32u,   // look-back spin bound hit
-    SEGF_EXOTIC = 64u,    // layout the workgroup decoder does not take (several blocks, > 32 KiB,
-                          // unsettled split): the wave-per-segment decoder redoes the stream
-};
 
 // InflateArgs::flags bit (internal): the stream is a piece of a larger stream (multi-GPU
 // scatter): a back-reference before its first byte is an error, not the stream-start no-op.
@@ -162,10 +145,12 @@ hipError_t launch_inflate_pj(const InflateArgs& A, uint32_t seg, hipStream_t st,
 // heavy != 0: when at most `limit` candidates span more than `heavy` bytes (counted on the
 // device into hl[1]), those are declined and listed in hl (hl[0] = count, the indices from
 // hl[2] on; ncand + 2 words) for launch_inflate_pj_list.
-// split: ncand words when A.slot is 64 KiB (the halves' split), else unused
+// split: ncand words when A.slot is 64 KiB (the halves' split), else unused; ncu: the device's
+// compute units (the grid of the one-wave resolve)
 hipError_t launch_inflate_lanes(const InflateArgs& A, uint32_t* tok, uint64_t* tokoff,
                                 uint32_t* ntok, uint32_t* caps, uint32_t heavy, uint32_t limit,
-                                uint32_t* hl, uint32_t* split, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+                                uint32_t* hl, uint32_t* split, int ncu, hipStream_t st, hipEvent_t ev0,
+                                hipEvent_t ev1);
 // mode 6: the workgroup decoder over the candidates listed in hl, `grid` persistent workgroups
 hipError_t launch_inflate_pj_list(const InflateArgs& A, uint32_t seg, const uint32_t* hl, uint32_t grid,
                                   hipStream_t st, hipEvent_t ev1);
@@ -176,41 +161,8 @@ struct ValidateWords {
 hipError_t launch_inflate_validate(const InflateArgs& A, ValidateWords* W, InflateResult* res,
                                    hipStream_t st);
 
-// block-parallel inflate of arbitrary streams (inflate_blocks.hip, path 5)
-struct FbUnit {         // per-unit record written by k_fb_pdecode / k_fb_decode
-    uint64_t start;     // stream bit of the unit's first token (a block header, or a token
-                        // boundary inside a block: region and repair units)
-    uint64_t end;       // stream bit where it stopped: past its last block, or (soft stop) the
-                        // first token boundary at or past its stop
-    uint64_t size;      // output bytes
-    uint64_t hdr;       // state at `end`: FB_AT_HEADER, else the code in force (FB_STATE_*)
-    uint32_t ntok;      // token words
-    uint32_t flags;     // SEGF_*
-};
-// Units and their stops (path 5).  stops[u]: the stream bit where unit u ends, with
-constexpr uint64_t FB_STOP_WEAK = 1ull << 63;  // a stored-header (weak) unit
-constexpr uint64_t FB_STOP_SOFT = 1ull << 62;  // the next unit starts inside a block: end at the
-                                               // first token boundary at or past the stop
-constexpr uint64_t FB_STOP_REGION = 1ull << 61;  // the head of a long gap between dynamic-header
-                                                 // starts: a first block that is not dynamic ends
-                                                 // the unit at once (the region map decodes the run)
-constexpr uint64_t FB_STOP_MASK = FB_STOP_REGION - 1;
-// A code state (FbUnit.hdr, the per-unit vhdr): the stream bit of the dynamic block header whose
-// code is in force, or FB_STATE_FIXED for the fixed code; FB_STATE_FINAL: that block has BFINAL.
-constexpr uint64_t FB_STATE_FIXED = 1ull << 62;
-constexpr uint64_t FB_STATE_FINAL = 1ull << 61;
-constexpr uint64_t FB_STATE_POS = FB_STATE_FINAL - 1;
-constexpr uint64_t FB_AT_HEADER = ~0ull;       // the unit ended at a block header
-// how a unit starts (vmode)
-enum : uint8_t {
-    FB_V_HEADER = 0,   // at a block header (bit 0, a scanned dynamic or stored header)
-    FB_V_EXACT = 2,    // exactly at its start bit inside a block whose code is vhdr (a repair)
-};
-constexpr uint32_t SEGF_SOFT = 1u << 30;  // internal: decode_huffman reached the soft stop
-// FbUnit flag (not an error): the unit's decode passed at least one block header after its
-// start (diagnostics)
-constexpr uint32_t SEGF_CROSSED = 1u << 29;
-constexpr uint32_t SEGF_ERRORS = ~(SEGF_FINAL | SEGF_CROSSED);
+// block-parallel inflate of arbitrary streams (inflate_blocks.hip, path 5; FbUnit and the unit
+// stops and code states: inflate_records.h)
 uint64_t fb_scan_chunks(uint64_t n);
 uint32_t fb_hits_per_chunk();
 // header scan of every bit offset: counts[nchunks], hits[nchunks * fb_hits_per_chunk()],
@@ -223,7 +175,6 @@ hipError_t launch_fb_scan(const uint32_t* in_words, uint64_t misalign, uint64_t 
 // candidates (device), max_count: the most there can be (sizes the grids).  keep (host memory
 // mapped into the device, or nullptr): the accepted starts, unordered, *nkeep of them (entries
 // past keep_cap dropped).  ph: DMX_FB_DEBUG counters (or nullptr)
-constexpr uint64_t FB_HIT_REJECT = 1ull << 63;
 hipError_t launch_fb_compact(const uint32_t* in_words, uint64_t misalign, uint64_t n, const uint32_t* counts,
                              const uint64_t* offs, const uint64_t* hits, uint64_t nchunks, uint64_t* list,
                              const uint64_t* pcount, uint64_t max_count, unsigned long long* ph, uint64_t* keep,
@@ -234,7 +185,6 @@ hipError_t launch_fb_compact(const uint32_t* in_words, uint64_t misalign, uint64
 // the region of each of the nsb super blocks, J = nsb * fb_region_nodes() words, visit = nsb
 // words (the node the path enters each super block at, ~0 = none: region chunk << 6 | f << 5 |
 // offset, chunks of fb_region_chunk_bits()), rstat = nreg words (FB_REGION_END / _LINK / other)
-constexpr uint32_t FB_REGION_END = 0x80000001u, FB_REGION_LINK = 0x80000002u;
 uint64_t fb_region_super_bits();
 uint64_t fb_region_chunk_bits();
 uint32_t fb_region_nodes();

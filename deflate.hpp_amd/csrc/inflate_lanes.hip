@@ -1465,7 +1465,8 @@ hipError_t launch_place_segments(const uint8_t* src, uint32_t slot, const uint64
 
 hipError_t launch_inflate_lanes(const InflateArgs& A, uint32_t* tok, uint64_t* tokoff,
                                 uint32_t* ntok, uint32_t* caps, uint32_t heavy, uint32_t limit,
-                                uint32_t* hl, uint32_t* split, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+                                uint32_t* hl, uint32_t* split, int ncu, hipStream_t st, hipEvent_t ev0,
+                                hipEvent_t ev1) {
     if (ev0) (void)hipEventRecord(ev0, st);
     const uint32_t g = (uint32_t)((A.ncand + 255) / 256);
     const uint8_t* const in = reinterpret_cast<const uint8_t*>(A.in_words) + A.misalign;  // stream byte 0
@@ -1497,13 +1498,6 @@ hipError_t launch_inflate_lanes(const InflateArgs& A, uint32_t* tok, uint64_t* t
         hipLaunchKernelGGL((k_inflate_lanes<LN_OUT_CAP, LN_LANES>), lg, dim3(64), 0, st, A, B);
         hipLaunchKernelGGL((k_inflate_resolve<LN_OUT_CAP, RS_NT>), dim3((uint32_t)A.ncand), dim3(RS_NT), 0, st, A, B);
         if (kRsSplit) {
-            static int ncu = 0;
-            if (!ncu) {
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-                    ncu = 256;
-            }
             const uint32_t g = (uint32_t)std::min<uint64_t>(A.ncand, (uint64_t)RS_TICKET_WG * (uint64_t)ncu);
             if (g) hipLaunchKernelGGL((k_inflate_resolve<LN_OUT_CAP, 64>), dim3(g), dim3(64), 0, st, A, B);
         }
