@@ -18,6 +18,9 @@
 //   kernels fold 1024 results at a time until one is left; the host applies the start value
 //   and the final complement.
 //
+// k_checksum_batch is the form for the framed batch calls: all buffers of a call in one launch, a
+// workgroup per buffer folding its blocks in sequence, lengths read from device memory.
+//
 // Misaligned buffers are read from the 16-byte boundary below them; the bytes before the
 // buffer are masked to zero, which leaves both sums unchanged (zero bytes add nothing to S1 and
 // S2 is weighted from the end; a zero-start CRC register stays zero over zero bytes).
@@ -60,6 +63,51 @@ __device__ __forceinline__ void ck_load_run(const uint8_t* vbase, uint64_t g, ui
 }
 
 // ---- Adler-32 ------------------------------------------------------------------------------
+// one 16 KiB block for k_checksum_batch: the lanes' runs summed with full block weights into the
+// per-wave words (ends with a barrier); adler_block_total then adds the waves' words (any one
+// thread).  k_adler_blocks below keeps the same steps written out: built from these functions it
+// compiles to 68 VGPRs instead of 46.
+__device__ __forceinline__ void adler_block_sums(const uint8_t* vbase, uint64_t g, uint64_t lead, uint64_t vend,
+                                                 uint32_t t, uint32_t* s1w, uint64_t* s2w) {
+    uint32_t w[16];
+    ck_load_run(vbase, g, lead, vend, w);
+    // s1 = sum x_r, s2 = sum (64 - r) x_r over the run
+    uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const uint32_t x = (w[k] >> (8 * b)) & 0xFFu;
+            s1 += x;
+            s2 += (uint32_t)(CK_RUN - (4 * k + b)) * x;
+        }
+    }
+    // block sums with full 16 KiB weights: S2 = sum_t s2_t + s1_t (CK_BLK - 64 (t + 1))
+    uint64_t S2 = (uint64_t)s2 + (uint64_t)s1 * (CK_BLK - CK_RUN * (t + 1));
+    uint32_t S1 = s1;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        S1 += (uint32_t)__shfl_xor((int)S1, d, 64);
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)S2, d, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(S2 >> 32), d, 64);
+        S2 += ((uint64_t)hi << 32) | lo;
+    }
+    if ((t & 63) == 0) {
+        s1w[t >> 6] = S1;
+        s2w[t >> 6] = S2;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ uint2 adler_block_total(const uint32_t* s1w, const uint64_t* s2w) {
+    uint64_t a = 0, b = 0;
+#pragma unroll
+    for (int i = 0; i < (int)(CK_NT / 64); i++) {
+        a += s1w[i];
+        b += s2w[i];
+    }
+    return make_uint2((uint32_t)(a % ADLER_MOD), (uint32_t)(b % ADLER_MOD));
+}
+
 __global__ __launch_bounds__(CK_NT) void k_adler_blocks(const uint8_t* vbase, uint64_t lead, uint64_t vend,
                                                         uint2* part) {
     __shared__ uint64_t s2w[CK_NT / 64];
@@ -193,21 +241,16 @@ __device__ uint32_t crc_tree_fold(uint32_t R, uint64_t len, uint32_t* sR, uint64
     return sR[0];
 }
 
-__global__ __launch_bounds__(CK_NT) void k_crc_blocks(const uint8_t* vbase, uint64_t lead, uint64_t vend,
-                                                      CrcPow X, uint32_t* part, uint64_t* plen) {
-    __shared__ uint32_t T[256];
-    __shared__ uint32_t sR[CK_NT];
-    __shared__ uint64_t sL[CK_NT];
-    const uint32_t t = threadIdx.x;
-    {
-        uint32_t c = t;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
-        T[t] = c;
-    }
-    const uint64_t g = (uint64_t)blockIdx.x * CK_NT + t;
-    uint32_t w[16];
-    ck_load_run(vbase, g, lead, vend, w);
-    __syncthreads();
+// the byte-wise table of the reflected polynomial, one entry per thread (CK_NT == 256)
+__device__ __forceinline__ void crc_make_table(uint32_t* T, uint32_t t) {
+    uint32_t c = t;
+    for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
+    T[t] = c;
+}
+// one 16 KiB block: every lane's zero-start register over its run, folded over the workgroup;
+// returns the block's register, its byte count is in sL[0]
+__device__ __forceinline__ uint32_t crc_block(const uint32_t (&w)[16], uint64_t g, uint64_t lead, uint64_t vend,
+                                              const uint32_t* T, uint32_t* sR, uint64_t* sL, const CrcPow& X) {
     const uint64_t b0 = g * CK_RUN;
     // valid bytes of the run that lie before the end; leading masked zeros are fed through the
     // zero-start register (it stays zero), trailing bytes past vend are not fed at all
@@ -223,7 +266,21 @@ __global__ __launch_bounds__(CK_NT) void k_crc_blocks(const uint8_t* vbase, uint
     }
     const uint64_t len = nfeed > nlead ? nfeed - nlead : 0u;  // bytes of the buffer in this run
     // a run holding only leading zeros has R = 0 and length 0: it folds as the identity
-    const uint32_t Rb = crc_tree_fold<CK_NT>(nfeed > nlead ? R : 0u, len, sR, sL, 6, X);
+    return crc_tree_fold<CK_NT>(nfeed > nlead ? R : 0u, len, sR, sL, 6, X);
+}
+
+__global__ __launch_bounds__(CK_NT) void k_crc_blocks(const uint8_t* vbase, uint64_t lead, uint64_t vend,
+                                                      CrcPow X, uint32_t* part, uint64_t* plen) {
+    __shared__ uint32_t T[256];
+    __shared__ uint32_t sR[CK_NT];
+    __shared__ uint64_t sL[CK_NT];
+    const uint32_t t = threadIdx.x;
+    crc_make_table(T, t);
+    const uint64_t g = (uint64_t)blockIdx.x * CK_NT + t;
+    uint32_t w[16];
+    ck_load_run(vbase, g, lead, vend, w);
+    __syncthreads();
+    const uint32_t Rb = crc_block(w, g, lead, vend, T, sR, sL, X);
     if (t == 0) {
         part[blockIdx.x] = Rb;
         plen[blockIdx.x] = sL[0];
@@ -242,6 +299,85 @@ __global__ __launch_bounds__(1024) void k_crc_tree(const uint32_t* inR, const ui
     if (threadIdx.x == 0) {
         outR[blockIdx.x] = Rb;
         outL[blockIdx.x] = sL[0];
+    }
+}
+
+// ---- batched: every buffer of a framed batch call in one launch ---------------------------------
+// A persistent grid of 256-thread workgroups draws buffer indices from *ticket (as k_inflate_batch
+// does).  The workgroup walks its buffer's 16 KiB blocks with the per-block code above and folds
+// them in sequence: Adler by the (N - E) S1 rule of k_adler_fold, CRC by R = R x^(8 len) xor
+// R_block.  The result in side[k].ck is final: Adler-32 from 1, CRC-32 from 0 with the
+// complement applied (crc32_finish, on the device).
+// res == nullptr (deflate): buffer k is desc[k].in, desc[k].n bytes.  Otherwise (inflate): it is
+// desc[k].out with the length the batch decoder left in res[k].bytes -- device memory only -- and
+// only streams that decoded (res[k].status and side[k].status both DMX_OK, so bytes <= cap) are
+// summed.  Pointers have any alignment; the masking of ck_load_run keeps the neighbours' bytes out.
+__global__ __launch_bounds__(CK_NT) void k_checksum_batch(const InflateBatchDesc* desc, const ::dmx_batch_result* res,
+                                                          FrameHead* side, uint64_t count, int crc, CrcPow X,
+                                                          unsigned int* ticket) {
+    __shared__ uint32_t T[256];
+    __shared__ uint32_t sR[CK_NT];
+    __shared__ uint64_t sL[CK_NT];
+    __shared__ uint64_t s2w[CK_NT / 64];
+    __shared__ uint32_t s1w[CK_NT / 64];
+    __shared__ uint32_t sk;
+    const uint32_t t = threadIdx.x;
+    crc_make_table(T, t);
+    for (;;) {
+        __syncthreads();  // the table; the last buffer's reads of sk and the fold words
+        if (t == 0) sk = atomicAdd(ticket, 1u);
+        __syncthreads();
+        const uint64_t k = sk;
+        if (k >= count) break;
+        const uint8_t* p;
+        uint64_t n;
+        if (res) {
+            if (res[k].status != DMX_OK || side[k].status != DMX_OK) continue;
+            p = desc[k].out;
+            n = res[k].bytes;
+        } else {
+            p = desc[k].in;
+            n = desc[k].n;
+        }
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p) & ~(uintptr_t)15;
+        const uint8_t* const vbase = reinterpret_cast<const uint8_t*>(a);
+        const uint64_t lead = reinterpret_cast<uintptr_t>(p) - a;
+        const uint64_t vend = lead + n;
+        const uint64_t nblk = n ? (vend + CK_BLK - 1) / CK_BLK : 0;  // (an empty buffer is not read)
+        uint64_t A = 0, B = 0;  // thread 0: the running sums / register
+        uint32_t R = 0;
+        for (uint64_t blk = 0; blk < nblk; blk++) {
+            const uint64_t g = blk * CK_NT + t;
+            if (crc) {
+                uint32_t w[16];
+                ck_load_run(vbase, g, lead, vend, w);
+                const uint32_t Rb = crc_block(w, g, lead, vend, T, sR, sL, X);
+                if (t == 0) {
+                    const uint64_t len = sL[0];
+                    R = gf_mul(R, len == CK_BLK ? X.xp[14] : gf_xpow8(len, X)) ^ Rb;
+                }
+            } else {
+                adler_block_sums(vbase, g, lead, vend, t, s1w, s2w);
+                if (t == 0) {
+                    const uint2 s = adler_block_total(s1w, s2w);
+                    const int64_t dist = (int64_t)vend - (int64_t)((blk + 1) * CK_BLK);  // < 0 only for the last block
+                    int64_t f = dist % (int64_t)ADLER_MOD;
+                    if (f < 0) f += ADLER_MOD;
+                    A = (A + s.x) % ADLER_MOD;
+                    B = (B + s.y + (uint64_t)f * s.x % ADLER_MOD) % ADLER_MOD;
+                }
+            }
+            __syncthreads();  // the next block reuses the fold words
+        }
+        if (t == 0) {
+            if (crc) {
+                side[k].ck = ~(gf_mul(0xFFFFFFFFu, gf_xpow8(n, X)) ^ R);
+            } else {
+                A = (A + 1) % ADLER_MOD;  // start value 1: a0 = 1, b0 = 0
+                B = (B + n % ADLER_MOD) % ADLER_MOD;
+                side[k].ck = (uint32_t)((B << 16) | A);
+            }
+        }
     }
 }
 
@@ -317,6 +453,23 @@ hipError_t launch_crc32_raw(const uint8_t* d, uint64_t n, void* scratch, uint32_
         unit += 10;
     }
     return hipMemcpyAsync(d_out, R0, 4, hipMemcpyDeviceToDevice, st);
+}
+
+hipError_t launch_checksum_batch(const InflateBatchDesc* desc, const ::dmx_batch_result* res, FrameHead* side,
+                                 uint64_t count, bool crc, unsigned int* ticket, hipStream_t st) {
+    static const CrcPow X = make_pow();
+    if (!count) return hipSuccess;
+    int dev = 0, ncu = 0, per = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_checksum_batch, CK_NT, 0);
+    const uint64_t fit = (uint64_t)max(ncu, 1) * (uint64_t)max(per, 1);
+    const uint32_t grid = (uint32_t)(count < fit ? count : fit);
+    const hipError_t e = hipMemsetAsync(ticket, 0, sizeof(unsigned int), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_checksum_batch, dim3(grid), dim3(CK_NT), 0, st, desc, res, side, count, crc ? 1 : 0, X,
+                       ticket);
+    return hipGetLastError();
 }
 
 uint32_t crc32_finish(uint32_t raw, uint64_t n, uint32_t init) {

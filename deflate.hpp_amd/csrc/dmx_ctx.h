@@ -77,6 +77,7 @@ struct dmx_ctx {
     DevBuf fbJraw, fbJsub, fbcbit, fbucb;  // regions: chunk maps, sub-chunk entries, chunk entries, unit chunk
     DevBuf ck;  // checksum scratch (checksum.hip) + the 4-byte result at its start
     DevBuf btab, bres;  // batch calls: the uploaded tables / descriptors; the results + the ticket
+    DevBuf fdesc;       // framed batch deflate: {plain input, size, framed output, capacity} per buffer
     bool timing = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_df = nullptr;          // end of the last deflate's work (its scratch is reused)

@@ -199,9 +199,20 @@ int deflate_device_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, int level, 
 // the dictionary's last Du bytes (DeflateBatchSeg); the later segments are ordinary -- the
 // dictionary has left their window.  The segment count stays <= ceil(n / 16384), which
 // dmx_deflate_bound allows for.  Levels 0 and 1 have no matcher: their table is the plain one.
+// A framed call (fp != nullptr, dmx_deflate_batch_framed_device): the arrays describe the raw
+// streams inside the frames; after the deflate, k_checksum_batch sums the plain inputs and
+// k_frame_write adds headers and trailers and rewrites the results, before the one read-back.
+struct FramePlan {
+    uint32_t format;                // DMX_FRAME_*
+    int level;                      // deflate: the level the header states
+    bool verify;                    // inflate: DMX_BATCH_VERIFY
+    const InflateBatchDesc* hdesc;  // deflate: count x {plain input, size, framed output, capacity}
+};
+int checksum_locked(dmx_ctx* c, bool crc, const uint8_t* d, size_t n, uint32_t init, uint32_t* out, hipStream_t st);
+
 int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count, int level,
                          uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, hipStream_t st,
-                         const uint8_t* d_dict = nullptr, size_t dict_len = 0) {
+                         const uint8_t* d_dict = nullptr, size_t dict_len = 0, const FramePlan* fp = nullptr) {
     if (level < 0 || level > 3) level = 1;  // as deflate_device_locked
     const uint32_t seg = c->seg;
     const uint32_t du = level >= 2 ? (uint32_t)std::min<size_t>(dict_len, kDeflateDictMax) : 0u;
@@ -246,10 +257,14 @@ int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
     if (c->df_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_df, 0));
     begin_timing(c, st);
     DeflateArgs A;
-    if (!c->btab.ensure(bytes) || !c->bres.ensure(count * sizeof(dmx_batch_result)) ||
-        !deflate_scratch(c, A, nseg, nseg, level, seg))
+    // results | (framed) the checksum kernel's ticket | one FrameHead per buffer
+    const size_t res_bytes = count * sizeof(dmx_batch_result);
+    if (!c->btab.ensure(bytes) || !c->bres.ensure(res_bytes + (fp ? 16 + count * sizeof(FrameHead) : 0)) ||
+        (fp && !c->fdesc.ensure(count * sizeof(InflateBatchDesc))) || !deflate_scratch(c, A, nseg, nseg, level, seg))
         return DMX_ERR_NOMEM;
     HIPCHK(hipMemcpyAsync(c->btab.p, img, bytes, hipMemcpyHostToDevice, st));
+    if (fp)
+        HIPCHK(hipMemcpyAsync(c->fdesc.p, fp->hdesc, count * sizeof(InflateBatchDesc), hipMemcpyHostToDevice, st));
     uint8_t* const dimg = c->btab.as<uint8_t>();
     A.in = nullptr;
     A.n = 0;
@@ -265,9 +280,16 @@ int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
     A.bres = c->bres.as<dmx_batch_result>();
     A.nbuf = count;
     HIPCHK(launch_deflate(A, seg, st, c->timing ? c->ev[1] : nullptr, c->timing ? c->ev[2] : nullptr, du != 0));
+    if (fp) {
+        unsigned int* const d_ticket = reinterpret_cast<unsigned int*>(c->bres.as<uint8_t>() + res_bytes);
+        FrameHead* const d_side = reinterpret_cast<FrameHead*>(c->bres.as<uint8_t>() + res_bytes + 16);
+        HIPCHK(launch_checksum_batch(c->fdesc.as<InflateBatchDesc>(), nullptr, d_side, count,
+                                     fp->format != DMX_FRAME_ZLIB, d_ticket, st));
+        HIPCHK(launch_frame_write(c->fdesc.as<InflateBatchDesc>(), d_side, A.bres, count, fp->format, fp->level, st));
+    }
     HIPCHK(hipEventRecord(c->ev_df, st));
     c->df_pending = true;
-    HIPCHK(hipMemcpyAsync(res, c->bres.p, count * sizeof(dmx_batch_result), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(res, c->bres.p, res_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     end_timing(c, st);
     c->stats.segments = nseg;
@@ -297,9 +319,10 @@ constexpr size_t kBatchRouteBytes = 1u << 20;
 // dictionary, so no stream is routed then, whatever its size.
 int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count,
                          uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
-                         hipStream_t st, const uint8_t* d_dict = nullptr, size_t dict_len = 0) {
+                         hipStream_t st, const uint8_t* d_dict = nullptr, size_t dict_len = 0,
+                         const FramePlan* fp = nullptr) {
     std::vector<uint32_t> order, routed;
-    std::vector<uint64_t> image;
+    std::vector<uint64_t> image, back;
     const size_t off_order = count * sizeof(InflateBatchDesc);
     const uint32_t dl = (uint32_t)std::min<size_t>(dict_len, kInflateDictMax);
     try {
@@ -310,6 +333,7 @@ int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
         }
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return n[a] > n[b]; });
         image.resize((off_order + order.size() * 4 + 7) / 8);
+        if (fp) back.resize((count * (sizeof(dmx_batch_result) + sizeof(FrameHead)) + 32) / 8);
     } catch (const std::bad_alloc&) {
         return DMX_ERR_NOMEM;
     }
@@ -322,11 +346,20 @@ int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
     if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
     begin_timing(c, st);
     const size_t res_bytes = count * sizeof(dmx_batch_result);
-    if (!c->btab.ensure(image.size() * 8) || !c->bres.ensure(res_bytes + 16)) return DMX_ERR_NOMEM;
+    // results | the decoder's ticket | (framed) the checksum kernel's ticket | one FrameHead per buffer
+    const size_t back_bytes = fp ? res_bytes + 32 + count * sizeof(FrameHead) : res_bytes;
+    if (!c->btab.ensure(image.size() * 8) || !c->bres.ensure(back_bytes + 16)) return DMX_ERR_NOMEM;
     HIPCHK(hipMemcpyAsync(c->btab.p, img, image.size() * 8, hipMemcpyHostToDevice, st));
     if (c->timing) (void)hipEventRecord(c->ev[1], st);
     const uint32_t* const d_order = reinterpret_cast<const uint32_t*>(c->btab.as<uint8_t>() + off_order);
     unsigned int* const d_ticket = reinterpret_cast<unsigned int*>(c->bres.as<uint8_t>() + res_bytes);
+    FrameHead* const d_side = reinterpret_cast<FrameHead*>(c->bres.as<uint8_t>() + res_bytes + 32);
+    if (fp) {
+        // a routed stream's result is not written on the device: status -1 keeps it out of the
+        // checksum launch, and the host fills it in below
+        HIPCHK(hipMemsetAsync(c->bres.p, 0xFF, res_bytes, st));
+        HIPCHK(launch_frame_parse(c->btab.as<InflateBatchDesc>(), d_side, count, fp->format, st));
+    }
     if (dl)
         HIPCHK(launch_inflate_batch_dict(c->btab.as<InflateBatchDesc>(), d_order, order.size(),
                                          c->bres.as<dmx_batch_result>(), d_ticket, c->flags,
@@ -335,19 +368,39 @@ int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
         HIPCHK(launch_inflate_batch(c->btab.as<InflateBatchDesc>(), d_order, order.size(),
                                     c->bres.as<dmx_batch_result>(), d_ticket, c->flags, st));
     if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    if (fp) {
+        if (fp->verify)
+            HIPCHK(launch_checksum_batch(c->btab.as<InflateBatchDesc>(), c->bres.as<dmx_batch_result>(), d_side, count,
+                                         fp->format != DMX_FRAME_ZLIB, d_ticket + 4, st));
+        HIPCHK(launch_frame_verdict(d_side, c->bres.as<dmx_batch_result>(), count, fp->format, fp->verify, st));
+    }
     HIPCHK(hipEventRecord(c->ev_inf, st));
     c->inf_pending = true;
-    HIPCHK(hipMemcpyAsync(res, c->bres.p, res_bytes, hipMemcpyDeviceToHost, st));
+    // (framed: the side array rides in the same copy, for the routed streams' headers and trailers)
+    HIPCHK(hipMemcpyAsync(fp ? (void*)back.data() : (void*)res, c->bres.p, back_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     end_timing(c, st);
+    if (fp) std::memcpy(res, back.data(), res_bytes);
+    const FrameHead* const side =
+        fp ? reinterpret_cast<const FrameHead*>(reinterpret_cast<const uint8_t*>(back.data()) + res_bytes + 32) : nullptr;
     const dmx_stats batch_stats = c->stats;
     for (const uint32_t i : routed) {  // (each call synchronises on its own)
+        if (fp && side[i].status != DMX_OK) continue;  // a header error: k_frame_verdict reported it
+        const size_t head = fp ? (size_t)side[i].head : 0;
         size_t len = 0;
-        const int rc = inflate_device_locked(c, d_in[i], n[i], d_out[i], cap[i], &len, nullptr, st);
+        int rc = inflate_device_locked(c, d_in[i] + head, n[i] - head, d_out[i], cap[i], &len, nullptr, st);
         if (rc == DMX_ERR_NOMEM || rc == DMX_ERR_DEVICE) return rc;
+        const uint32_t path = c->stats.path;
+        if (fp && fp->verify && rc == DMX_OK) {  // the single-buffer launches: this stream synchronises anyway
+            const bool gz = fp->format != DMX_FRAME_ZLIB;
+            uint32_t ck = 0;
+            const int rk = checksum_locked(c, gz, d_out[i], len, gz ? 0u : 1u, &ck, st);
+            if (rk != DMX_OK) return rk;
+            if ((gz && side[i].isize != (uint32_t)len) || ck != side[i].want) rc = DMX_ERR_CHECKSUM;
+        }
         res[i].bytes = len;
         res[i].status = rc;
-        res[i].path = c->stats.path;
+        res[i].path = path;
     }
     c->stats = batch_stats;
     c->stats.segments = count;
@@ -697,7 +750,7 @@ void dmx_destroy(dmx_ctx* c) {
                       &c->ltokoff, &c->lntok, &c->lcaps, &c->lheavy, &c->rtmp, &c->rchain, &c->fbc, &c->fbh, &c->fbo, &c->fbl,
                       &c->fbs, &c->fbt, &c->fbk, &c->fbu, &c->fbch, &c->fbco, &c->fbcs, &c->fbimg, &c->fbstop, &c->fbwin, &c->fbopen, &c->fbvm, &c->fbvh,
                       &c->fbreg, &c->fbJ, &c->fbvis, &c->fbph,
-                      &c->ck, &c->btab, &c->bres})
+                      &c->ck, &c->btab, &c->bres, &c->fdesc})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -889,7 +942,8 @@ static int batch_host(dmx_ctx* c, const uint8_t* const* in, const size_t* n, siz
         // a result that fits the device area but not the caller's buffer
         if (res[i].status == DMX_OK && res[i].bytes > cap[i]) res[i].status = DMX_ERR_CAPACITY;
         const size_t w = std::min<size_t>({(size_t)res[i].bytes, cap[i], dcap[i]});
-        if (w && (res[i].status == DMX_OK || res[i].status == DMX_ERR_CAPACITY))
+        // (DMX_ERR_CHECKSUM, framed calls only: the decoded bytes are handed out all the same)
+        if (w && (res[i].status == DMX_OK || res[i].status == DMX_ERR_CAPACITY || res[i].status == DMX_ERR_CHECKSUM))
             std::memcpy(out[i], stage.data() + ooff[i], w);
     }
     return DMX_OK;
@@ -930,6 +984,210 @@ int dmx_inflate_batch_dict(dmx_ctx* c, const uint8_t* const* in, const size_t* n
 int dmx_inflate_batch(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, uint8_t* const* out,
                       const size_t* cap, dmx_batch_result* res, uint32_t flags) {
     return dmx_inflate_batch_dict(c, in, n, count, nullptr, 0, out, cap, res, flags);
+}
+
+// ---- framed batch calls: zlib / gzip / BGZF around the batch (frame_batch.hip) ---------------
+size_t dmx_batch_framed_bound(uint32_t format, size_t n) {
+    const uint32_t head = frame_head_bytes(format);
+    return head ? dmx_deflate_bound(n) + head + frame_tail_bytes(format) : 0;
+}
+
+extern "C++" {
+// The batch deflate writes each raw stream behind its header's place, into the capacity less
+// header and trailer (clamped at 0); a BGZF buffer above the block size is given nothing to do
+// and k_frame_write reports it.
+static int deflate_batch_framed_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count,
+                                       int level, uint32_t format, uint8_t* const* d_out, const size_t* cap,
+                                       dmx_batch_result* res, hipStream_t st) {
+    const size_t frame = frame_head_bytes(format) + frame_tail_bytes(format);
+    std::vector<InflateBatchDesc> desc;
+    std::vector<size_t> rn, rcap;
+    std::vector<uint8_t*> rout;
+    try {
+        desc.resize(count);
+        rn.resize(count);
+        rcap.resize(count);
+        rout.resize(count);
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    for (size_t i = 0; i < count; i++) {
+        if ((!d_in[i] && n[i]) || (!d_out[i] && cap[i])) return DMX_ERR_ARG;
+        const bool big = format == DMX_FRAME_BGZF && n[i] > kBgzfBlock;
+        desc[i] = InflateBatchDesc{d_in[i], n[i], d_out[i], cap[i]};
+        rn[i] = big ? 0 : n[i];
+        rcap[i] = (big || cap[i] < frame) ? 0 : cap[i] - frame;
+        rout[i] = rcap[i] ? d_out[i] + frame_head_bytes(format) : nullptr;
+    }
+    const FramePlan fp{format, level, false, desc.data()};
+    return deflate_batch_locked(c, d_in, rn.data(), count, level, rout.data(), rcap.data(), res, st, nullptr, 0, &fp);
+}
+}  // extern "C++"
+
+static bool frame_format_ok(uint32_t format) { return frame_head_bytes(format) != 0; }
+
+int dmx_deflate_batch_framed_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count, int level,
+                                    uint32_t format, void* const* d_out, const size_t* cap, dmx_batch_result* res,
+                                    void* stream) {
+    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res) || !frame_format_ok(format)) return DMX_ERR_ARG;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;  // as dmx_deflate_batch_device
+    if (count == 0) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return deflate_batch_framed_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), n, count, level, format,
+                                       reinterpret_cast<uint8_t* const*>(d_out), cap, res, st);
+}
+
+int dmx_inflate_batch_framed_device(dmx_ctx* c, const void* const* d_in, const size_t* n, size_t count,
+                                    uint32_t format, void* const* d_out, const size_t* cap, dmx_batch_result* res,
+                                    uint32_t flags, void* stream) {
+    if (!batch_args_ok(c, d_in, n, count, d_out, cap, res) || !frame_format_ok(format) ||
+        (flags & ~(DMX_BATCH_NO_ROUTE | DMX_BATCH_VERIFY)))
+        return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const FramePlan fp{format, 0, (flags & DMX_BATCH_VERIFY) != 0, nullptr};
+    return inflate_batch_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), n, count,
+                                reinterpret_cast<uint8_t* const*>(d_out), cap, res, flags & DMX_BATCH_NO_ROUTE, st,
+                                nullptr, 0, &fp);
+}
+
+int dmx_deflate_batch_framed(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, int level,
+                             uint32_t format, uint8_t* const* out, const size_t* cap, dmx_batch_result* res) {
+    if (!batch_args_ok(c, in, n, count, out, cap, res) || !frame_format_ok(format)) return DMX_ERR_ARG;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    return batch_host(c, in, n, count, out, cap, res, nullptr, 0,
+                      [&](size_t i) { return std::min(cap[i], dmx_batch_framed_bound(format, n[i])); },
+                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc, const uint8_t*) {
+                          return deflate_batch_framed_locked(c, di, n, count, level, format, dou, dc, res, c->stream);
+                      });
+}
+
+int dmx_inflate_batch_framed(dmx_ctx* c, const uint8_t* const* in, const size_t* n, size_t count, uint32_t format,
+                             uint8_t* const* out, const size_t* cap, dmx_batch_result* res, uint32_t flags) {
+    if (!batch_args_ok(c, in, n, count, out, cap, res) || !frame_format_ok(format) ||
+        (flags & ~(DMX_BATCH_NO_ROUTE | DMX_BATCH_VERIFY)))
+        return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    const FramePlan fp{format, 0, (flags & DMX_BATCH_VERIFY) != 0, nullptr};
+    return batch_host(c, in, n, count, out, cap, res, nullptr, 0, [&](size_t i) { return cap[i]; },
+                      [&](const uint8_t* const* di, uint8_t* const* dou, const size_t* dc, const uint8_t*) {
+                          return inflate_batch_locked(c, di, n, count, dou, dc, res, flags & DMX_BATCH_NO_ROUTE,
+                                                      c->stream, nullptr, 0, &fp);
+                      });
+}
+
+// ---- BGZF files on host buffers: one framed batch call each -----------------------------------
+static const uint8_t kBgzfEof[kBgzfEofBytes] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43,
+                                                0x02, 0,    0x1b, 0,    0x03, 0, 0, 0, 0, 0,    0,    0, 0,    0};
+
+size_t dmx_bgzf_bound(size_t n) {
+    const size_t full = n / kBgzfBlock, rem = n % kBgzfBlock;
+    return full * dmx_batch_framed_bound(DMX_FRAME_BGZF, kBgzfBlock) +
+           (rem ? dmx_batch_framed_bound(DMX_FRAME_BGZF, rem) : 0) + kBgzfEofBytes;
+}
+
+int dmx_deflate_bgzf(dmx_ctx* c, const uint8_t* in, size_t n, int level, uint8_t* out, size_t cap, size_t* out_len) {
+    if (!c) c = dmx_default_ctx();
+    if (!c) return DMX_ERR_DEVICE;
+    if ((!in && n) || !out_len || !out) return DMX_ERR_ARG;
+    *out_len = 0;
+    const size_t nblk = (n + kBgzfBlock - 1) / kBgzfBlock;
+    const size_t slot = dmx_batch_framed_bound(DMX_FRAME_BGZF, kBgzfBlock);
+    std::vector<const uint8_t*> ins;
+    std::vector<uint8_t*> outs;
+    std::vector<size_t> ns, caps;
+    std::vector<dmx_batch_result> res;
+    std::vector<uint8_t> members;  // one slot per member; concatenated into `out` below
+    try {
+        ins.resize(nblk);
+        outs.resize(nblk);
+        ns.resize(nblk);
+        caps.resize(nblk);
+        res.resize(nblk);
+        members.resize(nblk * slot);
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    for (size_t i = 0; i < nblk; i++) {
+        ins[i] = in + i * kBgzfBlock;
+        ns[i] = std::min<size_t>(kBgzfBlock, n - i * kBgzfBlock);
+        outs[i] = members.data() + i * slot;
+        caps[i] = slot;
+    }
+    const int rc = dmx_deflate_batch_framed(c, ins.data(), ns.data(), nblk, level, DMX_FRAME_BGZF, outs.data(),
+                                            caps.data(), res.data());
+    if (rc != DMX_OK) return rc;
+    size_t total = kBgzfEofBytes;
+    for (size_t i = 0; i < nblk; i++) {
+        if (res[i].status != DMX_OK) return res[i].status;
+        total += res[i].bytes;
+    }
+    *out_len = total;
+    if (total > cap) return DMX_ERR_CAPACITY;
+    uint8_t* o = out;
+    for (size_t i = 0; i < nblk; i++) {
+        std::memcpy(o, outs[i], res[i].bytes);
+        o += res[i].bytes;
+    }
+    std::memcpy(o, kBgzfEof, kBgzfEofBytes);
+    return DMX_OK;
+}
+
+int dmx_inflate_bgzf(dmx_ctx* c, const uint8_t* in, size_t n, uint32_t flags, uint8_t** out, size_t* len) {
+    if (!c) c = dmx_default_ctx();
+    if (!c) return DMX_ERR_DEVICE;
+    if ((!in && n) || !out || !len || (flags & ~DMX_VERIFY)) return DMX_ERR_ARG;
+    *out = nullptr;
+    *len = 0;
+    std::vector<const uint8_t*> ins;
+    std::vector<uint8_t*> outs;
+    std::vector<size_t> ns, caps;
+    std::vector<dmx_batch_result> res;
+    size_t total = 0;
+    try {
+        for (uint64_t off = 0; off < n;) {  // the member chain, by BSIZE
+            BgzfMember m;
+            const int rc = bgzf_next(in, n, off, &m);
+            if (rc != DMX_OK) return rc;
+            ins.push_back(in + m.off);
+            ns.push_back((size_t)m.size);
+            caps.push_back(m.isize);
+            total += m.isize;
+            off += m.size;
+        }
+        outs.resize(ins.size());
+        res.resize(ins.size());
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    uint8_t* h = static_cast<uint8_t*>(std::malloc(total ? total : 1));
+    if (!h) return DMX_ERR_NOMEM;
+    size_t o = 0;
+    for (size_t i = 0; i < ins.size(); i++) {  // the layout: the prefix sum of ISIZE
+        outs[i] = h + o;
+        o += caps[i];
+    }
+    int rc = dmx_inflate_batch_framed(c, ins.data(), ns.data(), ins.size(), DMX_FRAME_BGZF, outs.data(), caps.data(),
+                                      res.data(), (flags & DMX_VERIFY) ? DMX_BATCH_VERIFY : 0u);
+    for (size_t i = 0; rc == DMX_OK && i < ins.size(); i++) {
+        rc = res[i].status;
+        // a member that decodes to more or fewer bytes than its ISIZE breaks the layout
+        if (rc == DMX_ERR_CAPACITY || (rc == DMX_OK && res[i].bytes != caps[i])) rc = DMX_ERR_CHECKSUM;
+    }
+    if (rc != DMX_OK) {
+        std::free(h);
+        return rc;
+    }
+    *out = h;
+    *len = total;
+    return DMX_OK;
 }
 
 int dmx_deflate(dmx_ctx* c, const uint8_t* in, size_t n, int level, uint8_t* out, size_t cap,
@@ -1148,31 +1406,10 @@ static int inflate_framed(dmx_ctx* c, bool gz, const uint8_t* in, size_t n, uint
     if ((!in && n) || !out || !len) return DMX_ERR_ARG;
     *out = nullptr;
     *len = 0;
-    size_t head = 0;
-    if (gz) {
-        if (n < 18) return DMX_ERR_OVERREAD;
-        if (in[0] != 0x1F || in[1] != 0x8B || in[2] != 8) return DMX_ERR_DATA;
-        const uint8_t flg = in[3];
-        head = 10;
-        if (flg & 4) {  // FEXTRA
-            if (head + 2 > n) return DMX_ERR_OVERREAD;
-            head += 2 + (size_t)(in[head] | (in[head + 1] << 8));
-        }
-        for (int z = 0; z < 2; z++) {  // FNAME, FCOMMENT: zero-terminated
-            if (flg & (8 << z)) {
-                while (head < n && in[head]) head++;
-                head++;
-            }
-        }
-        if (flg & 2) head += 2;  // FHCRC
-        if (head + 8 > n) return DMX_ERR_OVERREAD;
-    } else {
-        if (n < 6) return DMX_ERR_OVERREAD;
-        const uint32_t cmf = in[0], flg = in[1];
-        if ((cmf & 15) != 8 || (cmf >> 4) > 7 || (cmf * 256 + flg) % 31 != 0) return DMX_ERR_DATA;
-        if (flg & 0x20) return DMX_ERR_DATA;  // preset dictionary: not supported
-        head = 2;
-    }
+    // (container_parse.h: the parse the framed batch kernels run)
+    const FrameHead fh = parse_frame(gz ? DMX_FRAME_GZIP : DMX_FRAME_ZLIB, in, n);
+    if (fh.status != DMX_OK) return fh.status;
+    const size_t head = (size_t)fh.head;
     std::lock_guard<std::mutex> g(c->mu);
     DeviceGuard dg(c->device);
     if (!dg.ok) return DMX_ERR_DEVICE;
@@ -1184,17 +1421,8 @@ static int inflate_framed(dmx_ctx* c, bool gz, const uint8_t* in, size_t n, uint
         uint32_t ck = 0;
         rc = checksum_locked(c, gz, dev, tot, gz ? 0u : 1u, &ck, c->stream);
         if (rc != DMX_OK) return rc;
-        const uint8_t* t = in + n - (gz ? 8 : 4);
-        uint32_t want = 0;
-        if (gz) {
-            want = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) |
-                                   ((uint32_t)t[7] << 24);
-            if (isize != (uint32_t)tot) return DMX_ERR_CHECKSUM;
-        } else {
-            want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | (uint32_t)t[3];
-        }
-        if (ck != want) return DMX_ERR_CHECKSUM;
+        if (gz && fh.isize != (uint32_t)tot) return DMX_ERR_CHECKSUM;
+        if (ck != fh.want) return DMX_ERR_CHECKSUM;
     }
     uint8_t* h = static_cast<uint8_t*>(std::malloc(tot ? tot : 1));
     if (!h) return DMX_ERR_NOMEM;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/dmx.h"
+#include "container_parse.h"  // FrameHead, parse_frame (plain C++, shared with the CPU test)
 #include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
 
 namespace dmx {
@@ -247,5 +248,26 @@ hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* or
 hipError_t launch_inflate_batch_dict(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
                                      ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags,
                                      const uint8_t* dict, uint32_t dl, hipStream_t st);
+
+
+// framed batch calls (checksum.hip, frame_batch.hip; FrameHead and the parse: container_parse.h).
+// side holds one FrameHead per buffer.
+// launch_checksum_batch: side[k].ck = the Adler-32 (crc false) / CRC-32 of every buffer in one
+// launch.  res == nullptr: buffer k is desc[k].in, desc[k].n bytes (the deflate's plain input);
+// else desc[k].out with the length in res[k].bytes, for the buffers whose res[k].status and
+// side[k].status are DMX_OK (the inflate's output).  *ticket is zeroed by the launch.
+hipError_t launch_checksum_batch(const InflateBatchDesc* desc, const ::dmx_batch_result* res, FrameHead* side,
+                                 uint64_t count, bool crc, unsigned int* ticket, hipStream_t st);
+// inflate, before the decode: parses buffer k's header into side[k] and narrows desc[k] to the raw
+// stream (a header error leaves desc[k].n = 0: nothing is decoded)
+hipError_t launch_frame_parse(InflateBatchDesc* desc, FrameHead* side, uint64_t count, uint32_t format,
+                              hipStream_t st);
+// inflate, after the decode and the checksums: header errors and (verify) trailer verdicts into res
+hipError_t launch_frame_verdict(const FrameHead* side, ::dmx_batch_result* res, uint64_t count, uint32_t format,
+                                bool verify, hipStream_t st);
+// deflate, after the batch deflate wrote the raw streams at desc[k].out + head: headers, trailers
+// (side[k].ck) and the framed res[k]; desc[k] = {plain input, its size, framed output, its capacity}
+hipError_t launch_frame_write(const InflateBatchDesc* desc, const FrameHead* side, ::dmx_batch_result* res,
+                              uint64_t count, uint32_t format, int level, hipStream_t st);
 
 }  // namespace dmx

@@ -26,6 +26,11 @@ DMX_CFG_FB_SERIAL = 2
 DMX_VERIFY = 1
 DMX_DEFLATE_NOT_FINAL = 1
 DMX_BATCH_NO_ROUTE = 1
+DMX_BATCH_VERIFY = 2
+DMX_FRAME_ZLIB = 1
+DMX_FRAME_GZIP = 2
+DMX_FRAME_BGZF = 3
+FRAME = {"zlib": DMX_FRAME_ZLIB, "gzip": DMX_FRAME_GZIP, "bgzf": DMX_FRAME_BGZF}
 BATCH_PATH = 6  # dmx_batch_result.path of a stream the batch decoder took
 
 CORPUS = {"zeros": 0, "repeat": 1, "random": 2, "text": 3, "mixed": 4, "bmp": 5}
@@ -42,6 +47,9 @@ EXPORTS = [
     "dmx_inflate_device_async", "dmx_deflate_batch_device", "dmx_inflate_batch_device",
     "dmx_deflate_batch", "dmx_inflate_batch", "dmx_deflate_batch_dict_device",
     "dmx_inflate_batch_dict_device", "dmx_deflate_batch_dict", "dmx_inflate_batch_dict",
+    "dmx_batch_framed_bound", "dmx_deflate_batch_framed_device", "dmx_inflate_batch_framed_device",
+    "dmx_deflate_batch_framed", "dmx_inflate_batch_framed", "dmx_bgzf_bound", "dmx_deflate_bgzf",
+    "dmx_inflate_bgzf",
 ]
 
 
@@ -134,6 +142,17 @@ def lib():
     L.dmx_inflate_batch_dict_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, brp, ctypes.c_uint32, vp]
     L.dmx_deflate_batch_dict.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp, sz, vp, vp, brp]
     L.dmx_inflate_batch_dict.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, brp, ctypes.c_uint32]
+    u32 = ctypes.c_uint32
+    L.dmx_batch_framed_bound.argtypes = [u32, sz]
+    L.dmx_batch_framed_bound.restype = sz
+    L.dmx_deflate_batch_framed_device.argtypes = [vp, vp, vp, sz, ctypes.c_int, u32, vp, vp, brp, vp]
+    L.dmx_inflate_batch_framed_device.argtypes = [vp, vp, vp, sz, u32, vp, vp, brp, u32, vp]
+    L.dmx_deflate_batch_framed.argtypes = [vp, vp, vp, sz, ctypes.c_int, u32, vp, vp, brp]
+    L.dmx_inflate_batch_framed.argtypes = [vp, vp, vp, sz, u32, vp, vp, brp, u32]
+    L.dmx_bgzf_bound.argtypes = [sz]
+    L.dmx_bgzf_bound.restype = sz
+    L.dmx_deflate_bgzf.argtypes = [vp, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(sz)]
+    L.dmx_inflate_bgzf.argtypes = [vp, vp, sz, u32, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
     _lib = L
     return L
 
@@ -466,6 +485,59 @@ class Context:
         vals = [o.raw[: r.bytes] if r.status == DMX_OK else DmxError(r.status, "inflate_batch")
                 for o, r in zip(outs, res)]
         return (vals, [(r.bytes, r.status, r.path) for r in res]) if with_results else vals
+
+    # ---- framed batch calls: zlib / gzip / BGZF around the batched API ---------------------
+    def deflate_batch_framed_device(self, ptrs, sizes, level, out_ptrs, caps, format="gzip", stream=None):
+        """dmx_deflate_batch_framed_device -> [(bytes, status, path)]: buffer i gets the zlib stream
+        / gzip member compress_zlib / compress_gzip gives for it alone, or one BGZF member."""
+        k, a_in, a_n, a_out, a_cap, res = self._batch_arrays(ptrs, sizes, out_ptrs, caps)
+        _check(lib().dmx_deflate_batch_framed_device(self.h, a_in, a_n, k, level, FRAME[format], a_out, a_cap, res,
+                                                     ctypes.c_void_p(stream) if stream else None),
+               "deflate_batch_framed_device")
+        return [(r.bytes, r.status, r.path) for r in res[:k]]
+
+    def inflate_batch_framed_device(self, ptrs, sizes, out_ptrs, caps, format="gzip", verify=True, no_route=False,
+                                    stream=None):
+        """dmx_inflate_batch_framed_device -> [(bytes, status, path)]; verify: check every trailer
+        on the GPU (DMX_BATCH_VERIFY)."""
+        k, a_in, a_n, a_out, a_cap, res = self._batch_arrays(ptrs, sizes, out_ptrs, caps)
+        fl = (DMX_BATCH_VERIFY if verify else 0) | (DMX_BATCH_NO_ROUTE if no_route else 0)
+        _check(lib().dmx_inflate_batch_framed_device(self.h, a_in, a_n, k, FRAME[format], a_out, a_cap, res, fl,
+                                                     ctypes.c_void_p(stream) if stream else None),
+               "inflate_batch_framed_device")
+        return [(r.bytes, r.status, r.path) for r in res[:k]]
+
+    def compress_batch_framed(self, datas, level=2, format="gzip"):
+        """zlib stream / gzip member / BGZF member of every buffer in one call: for "zlib" and
+        "gzip" equal to [compress_zlib(d, level) ...] / [compress_gzip(d, level) ...]."""
+        fmt = FRAME[format]
+        caps = [lib().dmx_batch_framed_bound(fmt, len(d)) for d in datas]
+        outs, res = self._batch_host("dmx_deflate_batch_framed", datas, caps, mid=(level, fmt))
+        for r in res:
+            _check(r.status, "deflate_batch_framed")
+        return [o.raw[: r.bytes] for o, r in zip(outs, res)]
+
+    def decompress_batch_framed(self, datas, caps, format="gzip", verify=True, no_route=False, with_results=False):
+        """Inflate every framed buffer in one call; elements as in decompress_batch: the decoded
+        bytes, or the DmxError that inflate_zlib / inflate_gzip would raise for that buffer alone."""
+        fl = (DMX_BATCH_VERIFY if verify else 0) | (DMX_BATCH_NO_ROUTE if no_route else 0)
+        outs, res = self._batch_host("dmx_inflate_batch_framed", datas, list(caps), mid=(FRAME[format],), tail=(fl,))
+        vals = [o.raw[: r.bytes] if r.status == DMX_OK else DmxError(r.status, "inflate_batch_framed")
+                for o, r in zip(outs, res)]
+        return (vals, [(r.bytes, r.status, r.path) for r in res]) if with_results else vals
+
+    def compress_bgzf(self, data, level=2):
+        """A BGZF file: members of 65280 input bytes plus the empty EOF member (dmx_deflate_bgzf)."""
+        data = bytes(data)
+        cap = lib().dmx_bgzf_bound(len(data))
+        out = ctypes.create_string_buffer(cap)
+        n = ctypes.c_size_t()
+        _check(lib().dmx_deflate_bgzf(self.h, data, len(data), level, out, cap, ctypes.byref(n)), "deflate_bgzf")
+        return out.raw[: n.value]
+
+    def decompress_bgzf(self, data, verify=True):
+        """BGZF file -> bytes, all members in one batch call (dmx_inflate_bgzf)."""
+        return self._unframed("dmx_inflate_bgzf", data, verify)
 
     def set_timing(self, on=True):
         _check(lib().dmx_set_timing(self.h, 1 if on else 0), "set_timing")

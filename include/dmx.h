@@ -324,6 +324,72 @@ int dmx_deflate_gzip(dmx_ctx* ctx, const uint8_t* in, size_t n, int level, uint8
 int dmx_inflate_zlib(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t** out, size_t* len);
 int dmx_inflate_gzip(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t** out, size_t* len);
 
+/* ---- framed batch calls: zlib / gzip / BGZF around the batched API (not in the reference) ----
+ * The batch calls above speak raw RFC 1951; the container calls above take one buffer per call.
+ * These frame and un-frame `count` buffers with one set of launches: the batch deflate / inflate
+ * unchanged, one launch that computes every buffer's Adler-32 / CRC-32 on the GPU (lengths read
+ * from device memory), and small kernels that write the headers and trailers or parse them and
+ * apply the verdicts.  Argument conventions, return value, res[i] and the one host
+ * synchronisation (plus the routed streams' own) are those of dmx_deflate_batch_device /
+ * dmx_inflate_batch_device.  An unknown format or flag is DMX_ERR_ARG.
+ *
+ * Deflate.  ZLIB / GZIP: buffer i's output is byte for byte what dmx_deflate_zlib /
+ * dmx_deflate_gzip writes for it alone on the same context (empty buffers, every level).  BGZF:
+ * one gzip member 1f 8b 08 04, MTIME 0, XFL and OS as dmx_deflate_gzip, XLEN 6, 42 43 02 00,
+ * BSIZE (member size - 1), the raw stream of dmx_deflate_device, CRC-32, ISIZE; a buffer with
+ * n[i] > 65280 gets res[i].status = DMX_ERR_ARG (65280 = htslib's block size; with
+ * dmx_deflate_bound(65280) + 26 = 65362 <= 65536 BSIZE always fits).  dmx_batch_framed_bound(format,
+ * n[i]) bounds output i.  A short cap[i]: DMX_ERR_CAPACITY, bytes = the framed size needed, nothing
+ * written past d_out[i] + cap[i].  A context with segment_bytes = 65536 returns DMX_ERR_ARG.
+ *
+ * Inflate.  res[i] has the status and bytes dmx_inflate_zlib / dmx_inflate_gzip report for buffer
+ * i alone (DMX_BATCH_VERIFY = their DMX_VERIFY): n[i] < 6 / < 18 is DMX_ERR_OVERREAD, a bad
+ * header or zlib's FDICT DMX_ERR_DATA; FEXTRA, FNAME, FCOMMENT, FHCRC are skipped; the trailer is
+ * the last 4 / 8 bytes of buffer i, so the caller gives each member's extent (one member per
+ * buffer).  GZIP accepts BGZF members; BGZF also requires the BC subfield with BSIZE + 1 == n[i]
+ * (DMX_ERR_DATA otherwise).  DMX_ERR_CHECKSUM (Adler-32, CRC-32 or ISIZE mismatch under
+ * DMX_BATCH_VERIFY): the decoded bytes are in d_out[i] and bytes is their count.
+ * DMX_ERR_CAPACITY is the plain batch's -- the first cap[i] bytes, bytes = the full size -- and
+ * carries no checksum verdict.  A header error has bytes = 0.  Streams are routed by n[i] as in
+ * the plain batch (DMX_BATCH_NO_ROUTE honoured) with the same framing and verification.
+ *
+ * Not covered: preset dictionaries, multi-member gzip without BSIZE, files, graph capture. */
+#define DMX_FRAME_ZLIB 1u   /* RFC 1950 */
+#define DMX_FRAME_GZIP 2u   /* RFC 1952, one member per buffer */
+#define DMX_FRAME_BGZF 3u   /* gzip member whose FEXTRA holds the BC subfield (BSIZE = member size - 1) */
+#define DMX_BATCH_VERIFY 2u /* inflate: check each trailer on the GPU */
+
+/* dmx_deflate_bound(n) + 6 / 18 / 26 for ZLIB / GZIP / BGZF; 0 for an unknown format */
+size_t dmx_batch_framed_bound(uint32_t format, size_t n);
+
+int dmx_deflate_batch_framed_device(dmx_ctx* ctx, const void* const* d_in, const size_t* n, size_t count,
+                                    int level, uint32_t format, void* const* d_out, const size_t* cap,
+                                    dmx_batch_result* res, void* stream);
+int dmx_inflate_batch_framed_device(dmx_ctx* ctx, const void* const* d_in, const size_t* n, size_t count,
+                                    uint32_t format, void* const* d_out, const size_t* cap,
+                                    dmx_batch_result* res, uint32_t flags, void* stream);
+/* host buffers */
+int dmx_deflate_batch_framed(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, size_t count, int level,
+                             uint32_t format, uint8_t* const* out, const size_t* cap, dmx_batch_result* res);
+int dmx_inflate_batch_framed(dmx_ctx* ctx, const uint8_t* const* in, const size_t* n, size_t count,
+                             uint32_t format, uint8_t* const* out, const size_t* cap, dmx_batch_result* res,
+                             uint32_t flags);
+
+/* BGZF files (the blocked gzip of BAM, VCF, tabix) on host buffers, one framed batch call each.
+ * Deflate: members of 65280 input bytes plus the 28-byte empty EOF member (n == 0: that member
+ * alone); dmx_bgzf_bound(n) bounds the file; DMX_ERR_CAPACITY sets *out_len to the size needed.
+ * Inflate: the member chain is walked on the host by BSIZE, the outputs are laid out by the prefix
+ * sum of the members' ISIZE and decoded by one batch call; *out is allocated by the library
+ * (dmx_free); flags: DMX_VERIFY.  An empty member (the EOF block) contributes nothing and may be
+ * absent.  Errors are the first failing member's, with nothing allocated: DMX_ERR_DATA (bad magic,
+ * no BC subfield), DMX_ERR_OVERREAD (the chain runs past n), DMX_ERR_CHECKSUM (a decoded size
+ * other than ISIZE, with or without DMX_VERIFY -- the layout rests on it; a CRC-32 mismatch under
+ * DMX_VERIFY). */
+size_t dmx_bgzf_bound(size_t n);
+int dmx_deflate_bgzf(dmx_ctx* ctx, const uint8_t* in, size_t n, int level, uint8_t* out, size_t cap,
+                     size_t* out_len);
+int dmx_inflate_bgzf(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t** out, size_t* len);
+
 /* ---- instrumentation -------------------------------------------------------------------- */
 typedef struct dmx_stats {
     double ms_main_kernel;  /* HIP-event time of the dominant kernel of the last call       */

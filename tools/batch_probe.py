@@ -12,13 +12,22 @@ profiles/batch_probe.json, which DESIGN quotes.
    records of the same generator; the batch calls with the dictionary against the same calls
    without it, alternated; ms per call and total compressed bytes of both.
 
+4. framed batch (--framed, writes profiles/batch_probe_framed.json): the shapes of part 1, level
+   2; the gzip-framed batch deflate against the plain batch deflate on the same buffers (the
+   difference is what checksums and framing cost), the framed batch inflate with and without
+   DMX_BATCH_VERIFY against the plain batch inflate, the loop over dmx_deflate_gzip /
+   dmx_inflate_gzip (host buffers, --loop-reps repetitions), and dmx_deflate_bgzf /
+   dmx_inflate_bgzf of 256 MiB of text with their GB/s.
+
 Timing: synchronised host wall clock around each call (every call ends in a host
 synchronisation of its own), WARM warm-up repetitions, then REPS measured ones; the median is
 reported with the minimum beside it.
 
-  python tools/batch_probe.py [--reps 20] [--quick] [--dict]
+  python tools/batch_probe.py [--reps 20] [--quick] [--dict | --framed [--loop-reps 20]]
 """
 import argparse
+import ctypes
+import gc
 import json
 import os
 import random
@@ -174,14 +183,123 @@ def dict_vs_plain(ctx, count, size, reps, dict_bytes=8192):
             "inflate_plain": summary(ip), "inflate_dict": summary(id_)}
 
 
+def alternate_all(fns, reps):
+    """Run the variants in turn, round after round: WARM unmeasured rounds, then reps measured."""
+    ts = [[] for _ in fns]
+    gc.collect()
+    gc.disable()  # the calls build lists of thousands of tuples; a collection inside a timed call
+    try:          # costs tens of ms and recurs with a period that can lock onto one variant
+        for k in range(WARM + reps):
+            for t, f in zip(ts, fns):
+                x = timed(f)
+                if k >= WARM:
+                    t.append(x)
+            gc.collect()
+    finally:
+        gc.enable()
+    return ts
+
+
+def framed_vs_plain(ctx, kind, count, size, reps, loop_reps):
+    data = dmx.corpus(kind, count * size, offset=1 << 20)
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    bound = (dmx.lib().dmx_batch_framed_bound(dmx.DMX_FRAME_GZIP, size) + 15) & ~15
+    d_c = [torch.empty(count * bound, dtype=torch.uint8, device="cuda") for _ in range(2)]  # plain, framed
+    d_o = torch.empty(count * size, dtype=torch.uint8, device="cuda")
+    ins = [d_in.data_ptr() + i * size for i in range(count)]
+    comps = [[t.data_ptr() + i * bound for i in range(count)] for t in d_c]
+    outs = [d_o.data_ptr() + i * size for i in range(count)]
+    sizes, bounds = [size] * count, [bound] * count
+    clen = [[], []]
+
+    def df_plain():
+        clen[0][:] = [r[0] for r in ctx.deflate_batch_device(ins, sizes, 2, comps[0], bounds)]
+
+    def df_framed():
+        res = ctx.deflate_batch_framed_device(ins, sizes, 2, comps[1], bounds, format="gzip")
+        assert all(r[1] == dmx.DMX_OK for r in res)
+        clen[1][:] = [r[0] for r in res]
+
+    def if_plain():
+        assert all(r[1] == dmx.DMX_OK for r in ctx.inflate_batch_device(comps[0], clen[0], outs, sizes))
+
+    def if_framed(verify):
+        def run():
+            res = ctx.inflate_batch_framed_device(comps[1], clen[1], outs, sizes, format="gzip", verify=verify)
+            assert all(r[:2] == (size, dmx.DMX_OK) for r in res)
+        return run
+
+    dp, dfr = alternate_all([df_plain, df_framed], reps)
+    assert [c + 18 for c in clen[0]] == clen[1]
+    ip, iv, inv = alternate_all([if_plain, if_framed(True), if_framed(False)], reps)
+    assert d_o.cpu().numpy().tobytes() == data, "round trip mismatch"
+
+    # the loop over the single-buffer container calls (host buffers, as their callers hold them)
+    lib, h = dmx.lib(), ctx.h
+    hin = ctypes.create_string_buffer(data, len(data))
+    hout = ctypes.create_string_buffer(count * bound)
+    base_in, base_out = ctypes.addressof(hin), ctypes.addressof(hout)
+    glen = [0] * count
+    n = ctypes.c_size_t()
+    p = ctypes.POINTER(ctypes.c_uint8)()
+
+    def df_loop():
+        for i in range(count):
+            rc = lib.dmx_deflate_gzip(h, base_in + i * size, size, 2, base_out + i * bound, bound, ctypes.byref(n))
+            assert rc == dmx.DMX_OK
+            glen[i] = n.value
+
+    def if_loop():
+        for i in range(count):
+            rc = lib.dmx_inflate_gzip(h, base_out + i * bound, glen[i], dmx.DMX_VERIFY, ctypes.byref(p), ctypes.byref(n))
+            assert rc == dmx.DMX_OK and n.value == size
+            lib.dmx_free(p)
+
+    dl, il = alternate_all([df_loop, if_loop], loop_reps)
+    assert glen == clen[1]
+    row = {"kind": kind, "count": count, "size": size, "level": 2, "format": "gzip", "compressed_bytes": sum(clen[1]),
+           "deflate_batch_plain": summary(dp), "deflate_batch_framed": summary(dfr),
+           "inflate_batch_plain": summary(ip), "inflate_batch_framed_verify": summary(iv),
+           "inflate_batch_framed_noverify": summary(inv),
+           "deflate_gzip_loop": summary(dl), "inflate_gzip_loop": summary(il)}
+    m = lambda k: row[k]["median_ms"]  # noqa: E731
+    row["deflate_framing_cost_ms"] = m("deflate_batch_framed") - m("deflate_batch_plain")
+    row["inflate_verify_cost_ms"] = m("inflate_batch_framed_verify") - m("inflate_batch_plain")
+    row["deflate_loop_over_framed_batch"] = m("deflate_gzip_loop") / m("deflate_batch_framed")
+    row["inflate_loop_over_framed_batch"] = m("inflate_gzip_loop") / m("inflate_batch_framed_verify")
+    return row
+
+
+def bgzf_file(ctx, nbytes, reps):
+    data = dmx.corpus("text", nbytes, offset=3 << 20)
+    f = []
+
+    def deflate():
+        f[:] = [ctx.compress_bgzf(data, 2)]
+
+    def inflate():
+        assert len(ctx.decompress_bgzf(f[0], verify=True)) == nbytes
+
+    td, ti = alternate_all([deflate, inflate], reps)
+    assert ctx.decompress_bgzf(f[0]) == data
+    row = {"kind": "text", "plain_bytes": nbytes, "file_bytes": len(f[0]), "level": 2,
+           "deflate_bgzf": summary(td), "inflate_bgzf": summary(ti)}
+    row["deflate_gb_per_s"] = nbytes / (row["deflate_bgzf"]["median_ms"] * 1e6)
+    row["inflate_gb_per_s"] = nbytes / (row["inflate_bgzf"]["median_ms"] * 1e6)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="an eighth of the buffer counts (a check of the tool)")
     ap.add_argument("--dict", action="store_true", help="only the preset-dictionary shapes (part 3)")
+    ap.add_argument("--framed", action="store_true", help="only the framed batch and BGZF shapes (part 4)")
+    ap.add_argument("--loop-reps", type=int, default=20, help="--framed: repetitions of the single-buffer loops")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "batch_probe_dict.json" if a.dict else "batch_probe.json")
+    name = "batch_probe_dict.json" if a.dict else "batch_probe_framed.json" if a.framed else "batch_probe.json"
+    a.out = a.out or os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
         sys.exit("batch_probe: no GPU")
     ctx = dmx.Context()
@@ -197,6 +315,30 @@ def main():
             with open(a.out, "w") as f:
                 json.dump(result, f, indent=1)
                 f.write("\n")
+        ctx.close()
+        return
+    if a.framed:
+        result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "loop_reps": a.loop_reps, "warmup": WARM,
+                  "quick": a.quick,
+                  "timing": "synchronised host wall clock per call, the variants alternated, Python's garbage "
+                            "collector run between rounds and not inside a timed call",
+                  "framed_vs_plain": [], "bgzf": []}
+
+        def save_framed():
+            with open(a.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+
+        row = bgzf_file(ctx, (256 << 20) // q, min(a.reps, 5))
+        result["bgzf"].append(row)
+        print(json.dumps(row), flush=True)
+        save_framed()
+        for count, size in ((4096 // q, 65536), (16384 // q, 4096)):
+            for kind in ("text", "mixed"):
+                row = framed_vs_plain(ctx, kind, count, size, a.reps, a.loop_reps)
+                result["framed_vs_plain"].append(row)
+                print(json.dumps(row), flush=True)
+                save_framed()
         ctx.close()
         return
     result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
