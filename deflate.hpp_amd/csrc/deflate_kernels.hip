@@ -99,6 +99,22 @@ constexpr bool DF_SKIP = DMX_DF_SKIP != 0;
 #ifndef DMX_DF_TERMRUN
 #define DMX_DF_TERMRUN 1
 #endif
+// level 2, with DMX_DF_RUNLEN: a segment with a terminal run also compares the round before the
+// run at the run's distance, so the parse knows from where on the data repeats (run_e); 0: from
+// the run's first round on
+#ifndef DMX_DF_RUNBACK
+#define DMX_DF_RUNBACK 1
+#endif
+// level 2, with DMX_DF_TERMRUN: the parse takes a match length from the proven run instead of
+// comparing bytes where both ends of the match lie inside it (see run_e and known_len)
+#ifndef DMX_DF_RUNLEN
+#define DMX_DF_RUNLEN 1
+#endif
+// level 2, segments with a terminal run: the parse walk's literal skip looks up to four bitmap
+// words ahead with the quad's four lanes (with DMX_DF_RUNLEN; see parse_walk)
+#ifndef DMX_DF_LITSKIP
+#define DMX_DF_LITSKIP 1
+#endif
 // the front kernel counts the symbols (the emission kernel skips its histogram pass)
 #ifndef DMX_DF_HIST
 #define DMX_DF_HIST 0
@@ -449,7 +465,8 @@ struct DfSmem {
     uint32_t tokmap[SEG / 32];  // token-start bitmap (parse walk; chunks share boundary words)
     uint16_t lasttok[NWALK_MAX + 1];  // last token start of each parse chunk
     uint32_t scan[4 * DF_NT / 64];
-    uint32_t sh[64];  // 44: run candidate, 46: mismatch tag, 48..62: divisor-period tags
+    uint32_t sh[64];  // 43: backward mismatch tag, 44: run candidate, 45 / 47: terminal run,
+                      // 46: mismatch tag, 48..62: divisor-period tags
     uint32_t hist[DMX_DF_HIST ? 320 : 1];  // the segment's symbol counts (see deflate_tok_stride)
 };
 
@@ -583,6 +600,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
     // in it the compiler spills its kernel arguments to scratch)
     constexpr bool TERMRUN = DF_SKIP && !L3 && SEG >= 32768 && DMX_DF_TERMRUN;
     constexpr uint32_t RUN_NONE = 0xFFFFFFFFu;
+    constexpr bool RUNLEN = TERMRUN && DMX_DF_RUNLEN;
+    constexpr bool RUNBACK = RUNLEN && DMX_DF_RUNBACK;
     DMX_PHASE(A.dbg, seg, 0);
 
     // ---- load the segment into LDS (16 B per lane when aligned) ------------------------
@@ -606,6 +625,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         if (t < NMAP) S.tokmap[t] = 0;
         if (t == 0) S.sh[46] = 0;  // the match rounds' mismatch tag (run continuation)
         if (TERMRUN && t == 1) S.sh[45] = RUN_NONE;  // its terminal run's first position
+        if (RUNBACK && t == 2) S.sh[43] = 0;  // the run's last mismatch in the round before it
         if (t >= 48 && t < 63) S.sh[t] = 0;  // its divisor-period tags
         if (DMX_DF_HIST && t < 320) S.hist[t] = 0;
         if (level >= 2)
@@ -622,6 +642,15 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // match rounds end at run_lo (a round's first position).  The round that finds the run
         // leaves both values in sh[45] and sh[47]: the rounds' loop carries no state for them.
         [[maybe_unused]] uint32_t run_lo = RUN_NONE, run_d = 0;
+        // The run's proven start (uniform), run_e <= run_lo: data[q] == data[q - run_d] for every
+        // q in [run_e, nb).  Next to the run's candidate fill (not in the round that proves the
+        // run: code there cost every segment's rounds ~1.4K cycles, runs or not) the words of the
+        // round before run_lo, not below run_d, are compared with the words run_d before them:
+        // one word per thread for half the threads, the end of the last mismatching byte by an
+        // atomicMax into sh[43], tagged with the round like sh[46].  Without a mismatch run_e is
+        // the first word compared; RUN_NONE without a terminal run.
+        [[maybe_unused]] uint32_t run_e = RUN_NONE;
+        [[maybe_unused]] float run_rcp = 0.f;  // 1 / run_d (known_len's multiple test)
         // ---- match candidates: rounds of 2*DF_NT positions, two per thread ---------------
         if (level >= 2) {
             // Table entries carry a fingerprint of the 4-byte key (product bits below the hash
@@ -1004,8 +1033,27 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 for (uint32_t i = i0 + t; i < i1; i += DF_NT) c4[i] = make_uint4(v, v, v, v);
                 const uint32_t p = 8 * i1 + t;
                 if (t < 16 && p < nb) S.cand[p] = (uint16_t)(p + 4 <= nb ? run_d : 0u);
+                if (RUNBACK) {  // (see run_e; the same alignbyte form as the rounds' forward test)
+                    constexpr uint32_t RP = 2 * DF_NT;
+                    const uint32_t bq = run_lo - RP + 4 * (uint32_t)t;
+                    if ((uint32_t)t < RP / 4 && bq >= run_d) {
+                        const uint32_t ia = (bq - run_d) >> 2;
+                        const uint32_t df = S.data32[bq >> 2] ^
+                                            __builtin_amdgcn_alignbyte(S.data32[ia + 1], S.data32[ia], (run_lo - run_d) & 3);
+                        if (df) atomicMax(&S.sh[43], ((run_lo / RP + 1) << 16) | (bq + 4 - ((uint32_t)__builtin_clz(df) >> 3)));
+                    }
+                }
             }
             __syncthreads();
+            if (RUNLEN && run_lo != RUN_NONE) {
+                constexpr uint32_t RP = 2 * DF_NT;
+                run_e = run_lo;
+                if (RUNBACK) {
+                    const uint32_t et = __builtin_amdgcn_readfirstlane(S.sh[43]);
+                    run_e = (et >> 16) == run_lo / RP + 1 ? et & 0xFFFFu : max(run_lo - RP, (run_d + 3) & ~3u);
+                }
+                run_rcp = __builtin_amdgcn_rcpf((float)run_d);
+            }
         }
         DMX_PHASE(A.dbg, seg, 2);
 
@@ -1017,7 +1065,13 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // walkers; a segment with one keeps 258-byte chunks, whose matches reach the maximum
         const uint32_t CH = (DMX_DF_ADAPT && level == 2 && !any_skip) ? (uint32_t)DF_CHUNK / 2 : (uint32_t)DF_CHUNK;
         const uint32_t nwalk = (nb - D + CH - 1) / CH;  // (the chunks start at D)
-        if (level >= 2 && (uint32_t)t < 4 * nwalk) {
+        // The walk exists twice in the 32 KiB level-2 kernel, chosen by a uniform branch: a segment
+        // with a terminal run takes the one with the known lengths and the quad-wide literal
+        // skip; every other segment (text, random) runs the plain walk, which both cost time.
+        auto parse_walk = [&](auto runc) {
+            constexpr bool RUNW = decltype(runc)::value;
+            constexpr bool KNOWN = RUNW;  // this copy takes known lengths (the segment has RUNLEN)
+            constexpr bool LITSKIP = RUNW && DMX_DF_LITSKIP;
             const uint32_t sub = t & 3;
             const bool lead = sub == 0;
             const uint32_t lo = D + (t >> 2) * CH;
@@ -1026,8 +1080,25 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 const uint32_t e = b - w * 32;
                 return (e >= 32 ? 0xFFFFFFFFu : ((1u << e) - 1u)) & (0xFFFFFFFFu << (a & 31));
             };
+            // The match at q with distance d reaches maxl without a compare when q and its
+            // source lie in the proven run: q >= run_e, d a multiple of run_d (a float-reciprocal
+            // quotient verified by one multiply) and q - d + run_d >= run_e.  Then every step
+            // back by run_d from q + i down to q + i - d stays inside [run_e - run_d, nb), so
+            // data[q + i] == data[q + i - d] for every i < hi - q.  (No run: run_e = RUN_NONE.)
+            [[maybe_unused]] auto known_len = [&](uint32_t q, uint32_t d) -> bool {
+                const uint32_t m = (uint32_t)((float)d * run_rcp + 0.5f);
+                return (q >= run_e) & (m * run_d == d) & (q - d + run_d >= run_e);
+            };
+            // matchlen4 of q against q - d; the length itself where it is known (a select on
+            // the compared length: a known match compares nothing)
+            auto len_at = [&](uint32_t q, uint32_t d, uint32_t maxl) -> uint32_t {
+                if (!KNOWN) return matchlen4(S.data32, q, q - d, maxl, sub);
+                const bool kn = known_len(q, d);
+                const uint32_t L = matchlen4(S.data32, q, q - d, kn ? 0u : maxl, sub);
+                return kn ? maxl : L;
+            };
             auto full_len = [&](uint32_t q) -> uint32_t {  // < 3 only on a fingerprint collision
-                return matchlen4(S.data32, q, q - S.cand[q], min(258u, hi - q), sub);
+                return len_at(q, S.cand[q], min(258u, hi - q));
             };
             uint32_t p = lo, w = lo >> 5, mw = S.mmap[w], tok = 0, lastp = lo;  // lastp: last token
             auto mbit = [&](uint32_t q) -> bool {
@@ -1044,8 +1115,24 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 const uint32_t m = mw & (0xFFFFFFFFu << (p & 31));
                 const uint32_t q = m ? w * 32 + __builtin_ctz(m) : 0xFFFFFFFFu;
                 if (q >= hi || !m) {  // literals to the end of the word (or chunk)
-                    const uint32_t e = min((w + 1) * 32, hi);
+                    uint32_t e = min((w + 1) * 32, hi);
                     tok |= bits_range(p, e, w);
+                    if (LITSKIP && e < hi) {
+                        // The quad looks ahead: lane sub inspects the (1 + sub)-th following
+                        // bitmap word, clipped at hi.  The lanes before the first word with a
+                        // match bit (or past hi) saw empty words: all literals, whose token bits
+                        // they OR in themselves (neighbouring chunks share boundary words).  The
+                        // walk resumes at that first word: up to five words per step.
+                        const uint32_t wl = w + 1 + sub, b0 = wl * 32;
+                        const bool in = b0 < hi;
+                        uint32_t x = in ? S.mmap[wl] : 0u;
+                        x = in && hi - b0 < 32 ? x & ((1u << (hi - b0)) - 1u) : x;
+                        uint32_t f = (!in || x) ? sub : 4u;
+                        f = min(f, xor_lane<1>(f));
+                        f = min(f, xor_lane<2>(f));
+                        if (sub < f) atomicOr(&S.tokmap[wl], bits_range(b0, min(b0 + 32, hi), wl));
+                        e = min((w + 1 + f) * 32, hi);
+                    }
                     lastp = e - 1;
                     p = e;
                     continue;
@@ -1094,7 +1181,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         while (pm) {
                             const uint32_t d1 = 1 + (uint32_t)__builtin_ctz(pm);
                             pm &= pm - 1;
-                            if (matchlen4(S.data32, p, p - d1, ml, sub) >= L) {
+                            if (len_at(p, d1, ml) >= L) {
                                 best = d1;
                                 break;
                             }
@@ -1136,7 +1223,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                             const int f = __builtin_ctz(pm);
                             pm &= pm - 1;
                             const uint32_t d1 = (uint32_t)__shfl((int)dk, qb + f, 64);
-                            if (matchlen4(S.data32, p, p - d1, ml, sub) >= L) {
+                            if (len_at(p, d1, ml) >= L) {
                                 best = d1;
                                 break;
                             }
@@ -1150,6 +1237,13 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             }
             if (tok && lead) atomicOr(&S.tokmap[w], tok);
             if (lead) S.lasttok[t >> 2] = (uint16_t)lastp;
+        };
+        if (level >= 2 && (uint32_t)t < 4 * nwalk) {
+            if constexpr (RUNLEN) {
+                if (run_lo != RUN_NONE) parse_walk(std::true_type{});
+                else parse_walk(std::false_type{});
+            } else
+                parse_walk(std::false_type{});
         }
         __syncthreads();
         DMX_PHASE(A.dbg, seg, 3);
