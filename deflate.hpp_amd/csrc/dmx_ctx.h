@@ -78,6 +78,10 @@ struct dmx_ctx {
     DevBuf ck;  // checksum scratch (checksum.hip) + the 4-byte result at its start
     DevBuf btab, bres;  // batch calls: the uploaded tables / descriptors; the results + the ticket
     DevBuf fdesc;       // framed batch deflate: {plain input, size, framed output, capacity} per buffer
+    // BGZF files in device memory: the deflate's member slots / the ranged read's edge members;
+    // the chain scratch (tile counts, candidates, jump tables, member table); descriptors + results
+    // (bgzt: the candidate scan's tile counts and offsets, which outlive the sizing of bgzc)
+    DevBuf bgzs, bgzc, bgzd, bgzt;
     bool timing = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_df = nullptr;          // end of the last deflate's work (its scratch is reused)

@@ -750,7 +750,7 @@ void dmx_destroy(dmx_ctx* c) {
                       &c->ltokoff, &c->lntok, &c->lcaps, &c->lheavy, &c->rtmp, &c->rchain, &c->fbc, &c->fbh, &c->fbo, &c->fbl,
                       &c->fbs, &c->fbt, &c->fbk, &c->fbu, &c->fbch, &c->fbco, &c->fbcs, &c->fbimg, &c->fbstop, &c->fbwin, &c->fbopen, &c->fbvm, &c->fbvh,
                       &c->fbreg, &c->fbJ, &c->fbvis, &c->fbph,
-                      &c->ck, &c->btab, &c->bres, &c->fdesc})
+                      &c->ck, &c->btab, &c->bres, &c->fdesc, &c->bgzs, &c->bgzc, &c->bgzd, &c->bgzt})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1188,6 +1188,279 @@ int dmx_inflate_bgzf(dmx_ctx* c, const uint8_t* in, size_t n, uint32_t flags, ui
     *out = h;
     *len = total;
     return DMX_OK;
+}
+
+// ---- BGZF files in device memory (bgzf_chain.hip) ---------------------------------------------
+extern "C++" {
+static size_t up16(size_t b) { return (b + 15) & ~size_t(15); }
+
+// The member chain of d_in[0, n), found on the device; two host synchronisations (the candidate
+// count sizes the scratch; then the member count, the plain bytes and the chain status).
+struct BgzfChain {
+    uint64_t members = 0, total = 0;
+    int status = DMX_OK;
+    BgzfCand* rows = nullptr;     // device: members entries, chain order
+    uint64_t* uoff = nullptr;     // device: their output offsets
+    BgzfChainHead* head = nullptr;
+};
+static int bgzf_chain_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, hipStream_t st, BgzfChain* ch) {
+    if (!n) return DMX_OK;  // no member, DMX_OK
+    const uint64_t nt = bgzf_tiles(d_in, n);
+    const size_t off_offs = up16(nt * 4), off_head = off_offs + up16(scan_words(nt) * 8);
+    if (!c->bgzt.ensure(off_head + 64)) return DMX_ERR_NOMEM;
+    uint8_t* const tb = c->bgzt.as<uint8_t>();
+    uint64_t* const tile_offs = reinterpret_cast<uint64_t*>(tb + off_offs);
+    ch->head = reinterpret_cast<BgzfChainHead*>(tb + off_head);
+    uint64_t* const d_ncand = reinterpret_cast<uint64_t*>(tb + off_head + 32);
+    HIPCHK(launch_bgzf_count(d_in, n, reinterpret_cast<uint32_t*>(tb), tile_offs, d_ncand, st));
+    uint64_t ncand = 0;
+    HIPCHK(hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ncand >= kBgzfNone) return DMX_ERR_NOMEM;  // (links are 32-bit candidate indices)
+    const uint32_t levels = bgzf_levels(ncand);
+    const size_t off_rows = up16(ncand * sizeof(BgzfCand)), off_J = off_rows * 2;
+    const size_t off_isz = off_J + up16((size_t)levels * ncand * 4), off_uoff = off_isz + up16(ncand * 4);
+    if (!c->bgzc.ensure(off_uoff + scan_words(ncand) * 8)) return DMX_ERR_NOMEM;
+    uint8_t* const cb = c->bgzc.as<uint8_t>();
+    ch->rows = reinterpret_cast<BgzfCand*>(cb + off_rows);
+    ch->uoff = reinterpret_cast<uint64_t*>(cb + off_uoff);
+    HIPCHK(launch_bgzf_chain(d_in, n, tile_offs, ncand, reinterpret_cast<BgzfCand*>(cb),
+                             reinterpret_cast<uint32_t*>(cb + off_J), ch->rows,
+                             reinterpret_cast<uint32_t*>(cb + off_isz), ch->uoff, ch->head, st));
+    BgzfChainHead h{};
+    HIPCHK(hipMemcpyAsync(&h, ch->head, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ch->members = h.members;
+    ch->total = h.total;
+    ch->status = h.status;
+    return DMX_OK;
+}
+
+// The framed batch inflate over device-built arrays: desc / order hold `count` members (identity
+// order, path 6 throughout: a member is at most 64 KiB), built by `build`.  One host
+// synchronisation, the read-back of the file status.
+struct BgzfBatch {
+    InflateBatchDesc* desc;
+    uint32_t* order;
+};
+template <class Build, class After>
+static int bgzf_inflate_locked(dmx_ctx* c, uint8_t* base, size_t count, bool verify, hipStream_t st, Build build,
+                               After after) {
+    // (base: c->bgzd behind what the caller keeps there)  desc | order | results | tickets | side | key
+    const size_t off_order = count * sizeof(InflateBatchDesc), off_res = off_order + up16(count * 4);
+    const size_t off_ticket = off_res + count * sizeof(dmx_batch_result), off_side = off_ticket + 32;
+    const size_t off_key = off_side + count * sizeof(FrameHead);
+    InflateBatchDesc* const desc = reinterpret_cast<InflateBatchDesc*>(base);
+    uint32_t* const order = reinterpret_cast<uint32_t*>(base + off_order);
+    dmx_batch_result* const res = reinterpret_cast<dmx_batch_result*>(base + off_res);
+    unsigned int* const ticket = reinterpret_cast<unsigned int*>(base + off_ticket);
+    FrameHead* const side = reinterpret_cast<FrameHead*>(base + off_side);
+    unsigned long long* const key = reinterpret_cast<unsigned long long*>(base + off_key);
+    HIPCHK(hipMemsetAsync(res, 0xFF, off_ticket - off_res, st));
+    HIPCHK(hipMemsetAsync(key, 0xFF, 8, st));
+    HIPCHK(build(BgzfBatch{desc, order}));
+    HIPCHK(launch_frame_parse(desc, side, count, DMX_FRAME_BGZF, st));
+    if (c->timing) (void)hipEventRecord(c->ev[1], st);
+    HIPCHK(launch_inflate_batch(desc, order, count, res, ticket, c->flags, st));
+    if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    if (verify) HIPCHK(launch_checksum_batch(desc, res, side, count, true, ticket + 4, st));
+    HIPCHK(launch_frame_verdict(side, res, count, DMX_FRAME_BGZF, verify, st));
+    HIPCHK(launch_bgzf_status(res, desc, count, key, st));
+    HIPCHK(after());
+    HIPCHK(hipEventRecord(c->ev_inf, st));
+    c->inf_pending = true;
+    unsigned long long k = 0;
+    HIPCHK(hipMemcpyAsync(&k, key, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    end_timing(c, st);
+    c->stats.segments = count;
+    c->stats.path = 6;
+    return k == ~0ull ? DMX_OK : (int)(int32_t)(uint32_t)k;
+}
+static size_t bgzf_batch_bytes(size_t count) {
+    return count * (sizeof(InflateBatchDesc) + sizeof(dmx_batch_result) + sizeof(FrameHead)) + up16(count * 4) + 48;
+}
+}  // extern "C++"
+
+int dmx_deflate_bgzf_device(dmx_ctx* c, const void* d_in, size_t n, int level, void* d_out, size_t cap,
+                            size_t* out_len, void* stream) {
+    if (!c || (!d_in && n) || !out_len || (!d_out && cap)) return DMX_ERR_ARG;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;  // as dmx_deflate_batch_framed_device
+    *out_len = 0;
+    const size_t nblk = (n + kBgzfBlock - 1) / kBgzfBlock;
+    if (nblk >= (size_t)DF_BATCH_LAST) return DMX_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (!nblk) {  // the EOF member alone
+        *out_len = kBgzfEofBytes;
+        if (cap < kBgzfEofBytes) return DMX_ERR_CAPACITY;
+        HIPCHK(hipMemcpyAsync(d_out, kBgzfEof, kBgzfEofBytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return DMX_OK;
+    }
+    // member i into slot i, as dmx_deflate_bgzf does on the host
+    const size_t slot = dmx_batch_framed_bound(DMX_FRAME_BGZF, kBgzfBlock);
+    std::vector<const uint8_t*> ins;
+    std::vector<uint8_t*> outs;
+    std::vector<size_t> ns, caps;
+    std::vector<dmx_batch_result> res;
+    try {
+        ins.resize(nblk);
+        outs.resize(nblk);
+        ns.resize(nblk);
+        caps.assign(nblk, slot);
+        res.resize(nblk);
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    const size_t off_offs = up16(nblk * 4), off_key = off_offs + up16(scan_words(nblk) * 8);
+    if (!c->bgzs.ensure(nblk * slot + 16) || !c->bgzc.ensure(off_key + 16 + sizeof(BgzfChainHead))) return DMX_ERR_NOMEM;
+    for (size_t i = 0; i < nblk; i++) {
+        ins[i] = static_cast<const uint8_t*>(d_in) + i * kBgzfBlock;
+        ns[i] = std::min<size_t>(kBgzfBlock, n - i * kBgzfBlock);
+        outs[i] = c->bgzs.as<uint8_t>() + i * slot;
+    }
+    const int rc = deflate_batch_framed_locked(c, ins.data(), ns.data(), nblk, level, DMX_FRAME_BGZF, outs.data(),
+                                               caps.data(), res.data(), st);
+    if (rc != DMX_OK) return rc;
+    // the members back to back into d_out, the EOF member behind them; the results are still in
+    // c->bres, where the batch left them
+    uint8_t* const cb = c->bgzc.as<uint8_t>();
+    unsigned long long* const key = reinterpret_cast<unsigned long long*>(cb + off_key);
+    BgzfChainHead* const head = reinterpret_cast<BgzfChainHead*>(cb + off_key + 16);
+    HIPCHK(hipMemsetAsync(key, 0xFF, 8, st));
+    HIPCHK(launch_bgzf_pack(c->bgzs.as<uint8_t>(), slot, c->bres.as<dmx_batch_result>(), nblk,
+                            reinterpret_cast<uint32_t*>(cb), reinterpret_cast<uint64_t*>(cb + off_offs), key,
+                            static_cast<uint8_t*>(d_out), cap, head, st));
+    HIPCHK(hipEventRecord(c->ev_df, st));
+    c->df_pending = true;
+    BgzfChainHead h{};
+    HIPCHK(hipMemcpyAsync(&h, head, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h.status == DMX_OK || h.status == DMX_ERR_CAPACITY) *out_len = (size_t)h.members;
+    c->stats.out_bytes = h.status == DMX_OK ? h.members : 0;
+    return h.status;
+}
+
+int dmx_bgzf_index_device(dmx_ctx* c, const void* d_in, size_t n, dmx_bgzf_entry* entries, size_t entry_cap,
+                          size_t* members, uint64_t* plain_bytes, void* stream) {
+    if (!c || (!d_in && n)) return DMX_ERR_ARG;
+    if (members) *members = 0;
+    if (plain_bytes) *plain_bytes = 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
+    begin_timing(c, st);
+    if (c->timing) (void)hipEventRecord(c->ev[1], st);
+    BgzfChain ch;
+    const int rc = bgzf_chain_locked(c, static_cast<const uint8_t*>(d_in), n, st, &ch);
+    if (rc != DMX_OK) return rc;
+    if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    HIPCHK(hipEventRecord(c->ev_inf, st));
+    c->inf_pending = true;
+    end_timing(c, st);
+    c->stats.segments = ch.members;
+    c->stats.in_bytes = n;
+    if (members) *members = (size_t)ch.members;
+    if (ch.status != DMX_OK) return ch.status;
+    if (plain_bytes) *plain_bytes = ch.total;
+    if (!entries) return DMX_OK;
+    if (entry_cap < ch.members + 1) return DMX_ERR_CAPACITY;
+    if (!ch.members) {
+        entries[0] = dmx_bgzf_entry{n, 0};
+        return DMX_OK;
+    }
+    const size_t bytes = (ch.members + 1) * sizeof(dmx_bgzf_entry);
+    if (!c->bgzd.ensure(bytes)) return DMX_ERR_NOMEM;
+    HIPCHK(launch_bgzf_entries(ch.rows, ch.uoff, ch.members, n, &ch.head->total, c->bgzd.as<dmx_bgzf_entry>(), st));
+    HIPCHK(hipEventRecord(c->ev_inf, st));
+    HIPCHK(hipMemcpyAsync(entries, c->bgzd.p, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return DMX_OK;
+}
+
+int dmx_inflate_bgzf_device(dmx_ctx* c, const void* d_in, size_t n, uint32_t flags, void* d_out, size_t cap,
+                            size_t* out_len, void* stream) {
+    if (!c || (!d_in && n) || !out_len || (!d_out && cap) || (flags & ~DMX_VERIFY)) return DMX_ERR_ARG;
+    *out_len = 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
+    begin_timing(c, st);
+    BgzfChain ch;
+    int rc = bgzf_chain_locked(c, static_cast<const uint8_t*>(d_in), n, st, &ch);
+    if (rc != DMX_OK) return rc;
+    if (ch.status != DMX_OK) return ch.status;
+    if (ch.total > cap) {  // before any member is looked at
+        *out_len = (size_t)ch.total;
+        return DMX_ERR_CAPACITY;
+    }
+    if (!ch.members) return DMX_OK;
+    if (ch.members >= (uint64_t)DF_BATCH_LAST) return DMX_ERR_NOMEM;
+    if (!c->bgzd.ensure(bgzf_batch_bytes(ch.members))) return DMX_ERR_NOMEM;
+    const uint8_t* const in = static_cast<const uint8_t*>(d_in);
+    uint8_t* const out = static_cast<uint8_t*>(d_out);
+    rc = bgzf_inflate_locked(
+        c, c->bgzd.as<uint8_t>(), ch.members, (flags & DMX_VERIFY) != 0, st,
+        [&](const BgzfBatch& b) { return launch_bgzf_desc(in, ch.rows, ch.uoff, ch.members, out, b.desc, b.order, st); },
+        [] { return hipSuccess; });
+    c->stats.in_bytes = n;
+    if (rc != DMX_OK) return rc;
+    c->stats.out_bytes = ch.total;
+    *out_len = (size_t)ch.total;
+    return DMX_OK;
+}
+
+int dmx_inflate_bgzf_range_device(dmx_ctx* c, const void* d_in, size_t n, const dmx_bgzf_entry* index, size_t members,
+                                  uint64_t uoffset, size_t len, uint32_t flags, void* d_out, void* stream) {
+    if (!c || (!d_in && n) || !index || (flags & ~DMX_VERIFY)) return DMX_ERR_ARG;
+    for (size_t k = 0; k < members; k++)
+        if (index[k + 1].coffset < index[k].coffset || index[k + 1].uoffset < index[k].uoffset) return DMX_ERR_ARG;
+    const uint64_t plain = index[members].uoffset;
+    if (index[members].coffset > n || uoffset > plain || len > plain - uoffset || uoffset < index[0].uoffset)
+        return DMX_ERR_ARG;
+    if (!len) return DMX_OK;
+    if (!d_out) return DMX_ERR_ARG;
+    // the members that overlap [u0, u1): from the last one that starts at or before u0 (it is not
+    // empty) up to the first entry at or behind u1
+    const uint64_t u0 = uoffset, u1 = uoffset + len;
+    const dmx_bgzf_entry* const e = index + members + 1;
+    const size_t k0 = (size_t)(std::upper_bound(index, e, u0, [](uint64_t u, const dmx_bgzf_entry& x) {
+                                   return u < x.uoffset;
+                               }) - index) - 1;
+    const size_t k1 = (size_t)(std::lower_bound(index, e, u1, [](const dmx_bgzf_entry& x, uint64_t u) {
+                                   return x.uoffset < u;
+                               }) - index);
+    const size_t count = k1 - k0;  // >= 1: index[k0].uoffset <= u0 < u1 <= index[k1].uoffset
+    if (count >= (size_t)DF_BATCH_LAST) return DMX_ERR_ARG;
+    const uint64_t edge0 = index[k0 + 1].uoffset - index[k0].uoffset, edge1 = index[k1].uoffset - index[k1 - 1].uoffset;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t idx_bytes = up16((count + 1) * sizeof(dmx_bgzf_entry));
+    if (!c->bgzs.ensure(edge0 + edge1 + 16) || !c->bgzd.ensure(idx_bytes + bgzf_batch_bytes(count))) return DMX_ERR_NOMEM;
+    if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
+    begin_timing(c, st);
+    dmx_bgzf_entry* const d_idx = c->bgzd.as<dmx_bgzf_entry>();
+    HIPCHK(hipMemcpyAsync(d_idx, index + k0, (count + 1) * sizeof(dmx_bgzf_entry), hipMemcpyHostToDevice, st));
+    const uint8_t* const in = static_cast<const uint8_t*>(d_in);
+    uint8_t* const out = static_cast<uint8_t*>(d_out);
+    uint8_t* const edge = c->bgzs.as<uint8_t>();
+    const int rc = bgzf_inflate_locked(
+        c, c->bgzd.as<uint8_t>() + idx_bytes, count, (flags & DMX_VERIFY) != 0, st,
+        [&](const BgzfBatch& b) {
+            return launch_bgzf_range_desc(in, d_idx, count, u0, u1, out, edge, b.desc, b.order, st);
+        },
+        [&] { return launch_bgzf_range_copy(d_idx, count, u0, u1, edge, out, st); });
+    c->stats.out_bytes = rc == DMX_OK ? len : 0;
+    return rc;
 }
 
 int dmx_deflate(dmx_ctx* c, const uint8_t* in, size_t n, int level, uint8_t* out, size_t cap,

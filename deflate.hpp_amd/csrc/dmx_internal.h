@@ -5,6 +5,7 @@
 
 #include "../../include/dmx.h"
 #include "container_parse.h"  // FrameHead, parse_frame (plain C++, shared with the CPU test)
+#include "bgzf_chain.h"       // BgzfCand and the chain steps (plain C++, shared with the CPU test)
 #include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
 
 namespace dmx {
@@ -269,5 +270,51 @@ hipError_t launch_frame_verdict(const FrameHead* side, ::dmx_batch_result* res, 
 // (side[k].ck) and the framed res[k]; desc[k] = {plain input, its size, framed output, its capacity}
 hipError_t launch_frame_write(const InflateBatchDesc* desc, const FrameHead* side, ::dmx_batch_result* res,
                               uint64_t count, uint32_t format, int level, hipStream_t st);
+
+// BGZF files in device memory (bgzf_chain.hip; the steps: bgzf_chain.h).
+struct BgzfChainHead {
+    uint64_t members;  // chain: members before the walk stops; launch_bgzf_pack: the file's bytes
+    uint64_t total;    // chain: plain bytes (the sum of ISIZE); launch_bgzf_pack: the members' bytes
+    int32_t status;    // chain: DMX_OK or where the serial walk stops; pack: DMX_OK, DMX_ERR_CAPACITY
+                       // or the first failing member's status
+    uint32_t pad_;
+};
+// tiles of the candidate scan (0 for n == 0); tile_counts holds as many words, tile_offs
+// scan_words(tiles) entries
+uint64_t bgzf_tiles(const uint8_t* in, uint64_t n);
+// *ncand = the offsets of in[0, n) where bgzf_next succeeds (n > 0)
+hipError_t launch_bgzf_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts, uint64_t* tile_offs,
+                             uint64_t* ncand, hipStream_t st);
+// The member table for the ncand the host read back: rows[r] (r < head->members) in chain order,
+// uoff = the exclusive prefix sum of their ISIZE, *head.  cands / rows / isz: ncand entries, J:
+// bgzf_levels(ncand) * ncand words, uoff: scan_words(ncand) entries.  ncand == 0 (and n == 0):
+// only *head is written.
+hipError_t launch_bgzf_chain(const uint8_t* in, uint64_t n, const uint64_t* tile_offs, uint64_t ncand,
+                             BgzfCand* cands, uint32_t* J, BgzfCand* rows, uint32_t* isz, uint64_t* uoff,
+                             BgzfChainHead* head, hipStream_t st);
+// entries[0 .. members]: member starts in both coordinate systems and the sentinel {n, *total}
+hipError_t launch_bgzf_entries(const BgzfCand* rows, const uint64_t* uoff, uint64_t members, uint64_t n,
+                               const uint64_t* total, ::dmx_bgzf_entry* entries, hipStream_t st);
+// desc[k] = {in + coff, size, out + uoff, isize}, order[k] = k: the arrays of the framed batch inflate
+hipError_t launch_bgzf_desc(const uint8_t* in, const BgzfCand* rows, const uint64_t* uoff, uint64_t members,
+                            uint8_t* out, InflateBatchDesc* desc, uint32_t* order, hipStream_t st);
+// ranged read over the index slice idx[0 .. count] (device copy): members inside the plain range
+// [u0, u1) decode into out, the first / last one into edge when they stick out; launch_bgzf_range_copy
+// moves their slices to out after the decode
+hipError_t launch_bgzf_range_desc(const uint8_t* in, const ::dmx_bgzf_entry* idx, uint64_t count, uint64_t u0,
+                                  uint64_t u1, uint8_t* out, uint8_t* edge, InflateBatchDesc* desc, uint32_t* order,
+                                  hipStream_t st);
+hipError_t launch_bgzf_range_copy(const ::dmx_bgzf_entry* idx, uint64_t count, uint64_t u0, uint64_t u1,
+                                  const uint8_t* edge, uint8_t* out, hipStream_t st);
+// *key (preset to all ones by the caller) = min over the members whose result is not DMX_OK of
+// index << 32 | (uint32_t)status, with dmx_inflate_bgzf's mapping to DMX_ERR_CHECKSUM
+hipError_t launch_bgzf_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
+                              unsigned long long* key, hipStream_t st);
+// deflate: member i (res[i].bytes at slots + i * stride) to out + the prefix sum, then the EOF
+// member; *head as above.  Nothing is written to out unless every member is DMX_OK and the file
+// fits cap.  sizes: count words, offs: scan_words(count) entries, *key preset to all ones.
+hipError_t launch_bgzf_pack(const uint8_t* slots, uint64_t stride, const ::dmx_batch_result* res, uint64_t count,
+                            uint32_t* sizes, uint64_t* offs, unsigned long long* key, uint8_t* out, uint64_t cap,
+                            BgzfChainHead* head, hipStream_t st);
 
 }  // namespace dmx

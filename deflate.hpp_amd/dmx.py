@@ -49,7 +49,8 @@ EXPORTS = [
     "dmx_inflate_batch_dict_device", "dmx_deflate_batch_dict", "dmx_inflate_batch_dict",
     "dmx_batch_framed_bound", "dmx_deflate_batch_framed_device", "dmx_inflate_batch_framed_device",
     "dmx_deflate_batch_framed", "dmx_inflate_batch_framed", "dmx_bgzf_bound", "dmx_deflate_bgzf",
-    "dmx_inflate_bgzf",
+    "dmx_inflate_bgzf", "dmx_deflate_bgzf_device", "dmx_bgzf_index_device", "dmx_inflate_bgzf_device",
+    "dmx_inflate_bgzf_range_device",
 ]
 
 
@@ -74,6 +75,11 @@ class Stats(ctypes.Structure):
 class BatchResult(ctypes.Structure):
     """dmx_batch_result: one buffer's outcome of a batch call."""
     _fields_ = [("bytes", ctypes.c_uint64), ("status", ctypes.c_int32), ("path", ctypes.c_uint32)]
+
+
+class BgzfEntry(ctypes.Structure):
+    """dmx_bgzf_entry: a member's start in the BGZF file and in the plain bytes."""
+    _fields_ = [("coffset", ctypes.c_uint64), ("uoffset", ctypes.c_uint64)]
 
 
 _lib = None
@@ -153,6 +159,12 @@ def lib():
     L.dmx_bgzf_bound.restype = sz
     L.dmx_deflate_bgzf.argtypes = [vp, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(sz)]
     L.dmx_inflate_bgzf.argtypes = [vp, vp, sz, u32, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+    u64 = ctypes.c_uint64
+    bep = ctypes.POINTER(BgzfEntry)
+    L.dmx_deflate_bgzf_device.argtypes = [vp, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(sz), vp]
+    L.dmx_bgzf_index_device.argtypes = [vp, vp, sz, bep, sz, ctypes.POINTER(sz), ctypes.POINTER(u64), vp]
+    L.dmx_inflate_bgzf_device.argtypes = [vp, vp, sz, u32, vp, sz, ctypes.POINTER(sz), vp]
+    L.dmx_inflate_bgzf_range_device.argtypes = [vp, vp, sz, bep, sz, u64, sz, u32, vp, vp]
     _lib = L
     return L
 
@@ -539,6 +551,62 @@ class Context:
         """BGZF file -> bytes, all members in one batch call (dmx_inflate_bgzf)."""
         return self._unframed("dmx_inflate_bgzf", data, verify)
 
+    # ---- BGZF files in device memory ------------------------------------------------------
+    @staticmethod
+    def _check_needed(rc, what, needed):
+        """_check; a DMX_ERR_CAPACITY error carries the size that was needed as .needed"""
+        if rc != DMX_OK:
+            e = DmxError(rc, what)
+            e.needed = needed if rc == DMX_ERR_CAPACITY else None
+            raise e
+
+    def deflate_bgzf_device(self, d_in, n, level, d_out, cap, stream=None):
+        """The BGZF file compress_bgzf gives for the n bytes at device pointer d_in, written at
+        device pointer d_out -> its size (dmx_deflate_bgzf_device; bgzf_bound(n) bounds it)."""
+        out_len = ctypes.c_size_t()
+        rc = lib().dmx_deflate_bgzf_device(self.h, ctypes.c_void_p(d_in), n, level, ctypes.c_void_p(d_out), cap,
+                                           ctypes.byref(out_len), ctypes.c_void_p(stream) if stream else None)
+        self._check_needed(rc, "deflate_bgzf_device", out_len.value)
+        return out_len.value
+
+    def bgzf_index_device(self, d_in, n, stream=None):
+        """The member index of a BGZF file in device memory, found on the GPU without decoding
+        (dmx_bgzf_index_device) -> (members + 1, 2) uint64 array: row k = member k's start in the
+        file and in the plain bytes, the last row the sentinel (n, plain bytes)."""
+        import numpy as np
+        sp = ctypes.c_void_p(stream) if stream else None
+        m = ctypes.c_size_t()
+        _check(lib().dmx_bgzf_index_device(self.h, ctypes.c_void_p(d_in), n, None, 0, ctypes.byref(m), None, sp),
+               "bgzf_index_device")
+        idx = np.zeros((m.value + 1, 2), dtype=np.uint64)
+        _check(lib().dmx_bgzf_index_device(self.h, ctypes.c_void_p(d_in), n,
+                                           idx.ctypes.data_as(ctypes.POINTER(BgzfEntry)), m.value + 1,
+                                           ctypes.byref(m), None, sp), "bgzf_index_device")
+        return idx
+
+    def inflate_bgzf_device(self, d_in, n, d_out, cap, verify=True, stream=None):
+        """decompress_bgzf of the file at device pointer d_in, into device pointer d_out -> the
+        plain size (dmx_inflate_bgzf_device)."""
+        out_len = ctypes.c_size_t()
+        rc = lib().dmx_inflate_bgzf_device(self.h, ctypes.c_void_p(d_in), n, DMX_VERIFY if verify else 0,
+                                           ctypes.c_void_p(d_out), cap, ctypes.byref(out_len),
+                                           ctypes.c_void_p(stream) if stream else None)
+        self._check_needed(rc, "inflate_bgzf_device", out_len.value)
+        return out_len.value
+
+    def inflate_bgzf_range_device(self, d_in, n, index, uoffset, length, d_out, verify=True, stream=None):
+        """Bytes [uoffset, uoffset + length) of the plain file into device pointer d_out, decoding
+        only the members that overlap them; index: what bgzf_index_device returned."""
+        import numpy as np
+        idx = np.ascontiguousarray(index, dtype=np.uint64)
+        if idx.ndim != 2 or idx.shape[1] != 2 or idx.shape[0] < 1:
+            raise ValueError("index must be an (m + 1, 2) array")
+        _check(lib().dmx_inflate_bgzf_range_device(self.h, ctypes.c_void_p(d_in), n,
+                                                   idx.ctypes.data_as(ctypes.POINTER(BgzfEntry)), idx.shape[0] - 1,
+                                                   uoffset, length, DMX_VERIFY if verify else 0,
+                                                   ctypes.c_void_p(d_out), ctypes.c_void_p(stream) if stream else None),
+               "inflate_bgzf_range_device")
+
     def set_timing(self, on=True):
         _check(lib().dmx_set_timing(self.h, 1 if on else 0), "set_timing")
 
@@ -568,3 +636,16 @@ def decompress(data, cap=None):
 
 def decompress_zlib(data):
     return default_context().decompress_zlib(data)
+
+
+def bgzf_bound(n):
+    return lib().dmx_bgzf_bound(n)
+
+
+def gzi_bytes(index):
+    """htslib's .gzi file for an index of Context.bgzf_index_device: a little-endian u64 count,
+    then the (compressed offset, uncompressed offset) pair of every member but the first; the
+    sentinel row is not stored."""
+    import struct
+    rows = [(int(c), int(u)) for c, u in index][1:-1]
+    return struct.pack("<Q", len(rows)) + b"".join(struct.pack("<QQ", c, u) for c, u in rows)

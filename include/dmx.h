@@ -353,7 +353,8 @@ int dmx_inflate_gzip(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, 
  * carries no checksum verdict.  A header error has bytes = 0.  Streams are routed by n[i] as in
  * the plain batch (DMX_BATCH_NO_ROUTE honoured) with the same framing and verification.
  *
- * Not covered: preset dictionaries, multi-member gzip without BSIZE, files, graph capture. */
+ * Not covered: preset dictionaries, multi-member gzip without BSIZE, files (BGZF files: the
+ * dmx_*_bgzf* calls below), graph capture. */
 #define DMX_FRAME_ZLIB 1u   /* RFC 1950 */
 #define DMX_FRAME_GZIP 2u   /* RFC 1952, one member per buffer */
 #define DMX_FRAME_BGZF 3u   /* gzip member whose FEXTRA holds the BC subfield (BSIZE = member size - 1) */
@@ -389,6 +390,58 @@ size_t dmx_bgzf_bound(size_t n);
 int dmx_deflate_bgzf(dmx_ctx* ctx, const uint8_t* in, size_t n, int level, uint8_t* out, size_t cap,
                      size_t* out_len);
 int dmx_inflate_bgzf(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t** out, size_t* len);
+
+/* BGZF files in device memory: the same files and results with DEVICE pointers (any alignment),
+ * plus the index and the ranged read that BGZF is blocked for.  The member chain is found on the
+ * device (candidate scan, links, pointer doubling from offset 0): the host does no per-member work
+ * for it.  The calls take the context mutex, are ordered against the context's other deflate /
+ * inflate work like their siblings, run on `stream` (NULL: the context's stream) and return after
+ * their last host synchronisation.  A null context is DMX_ERR_ARG; a context with n_gpus > 1 runs
+ * them on its first device.
+ *
+ * dmx_deflate_bgzf_device: the file dmx_deflate_bgzf writes for the same bytes, level and context,
+ * byte for byte, at d_out; *out_len = its size.  cap below that: DMX_ERR_CAPACITY, *out_len = the
+ * size needed, nothing written.  A context with segment_bytes = 65536 returns DMX_ERR_ARG.  Host
+ * synchronisations: 2 (the framed batch's results; the file size and status).
+ *
+ * dmx_bgzf_index_device: the chain walk alone, nothing is decoded and each trailer's ISIZE is
+ * trusted.  *members and *plain_bytes (either may be NULL) are set; with entries != NULL,
+ * members + 1 entries are written to HOST memory: entry k = member k's start in the file and in
+ * the plain bytes, the last one the sentinel {n, plain_bytes}.  entry_cap < members + 1 with
+ * entries != NULL: DMX_ERR_CAPACITY with *members set.  The chain's errors are dmx_inflate_bgzf's:
+ * DMX_ERR_DATA / DMX_ERR_OVERREAD at the member where the walk from offset 0 stops; n == 0 is
+ * DMX_OK with no member.  Host synchronisations: 3 (candidate count; member count, plain bytes and
+ * status; the entries) -- 2 without entries.
+ *
+ * dmx_inflate_bgzf_device: result and bytes of dmx_inflate_bgzf, at d_out; *out_len = the plain
+ * bytes.  plain bytes > cap: DMX_ERR_CAPACITY, *out_len = the size needed, nothing is decoded or
+ * written (the check precedes every member).  flags: DMX_VERIFY or 0.  On any other error
+ * *out_len = 0 and d_out may hold partial output.  Host synchronisations: 3 (candidate count;
+ * member count, plain bytes and chain status; the file status).
+ *
+ * dmx_inflate_bgzf_range_device: bytes [uoffset, uoffset + len) of the plain file, given the
+ * index (HOST memory, members + 1 entries as dmx_bgzf_index_device writes them).  Only the members
+ * that overlap the range are decoded: whole members straight into d_out, the at most two edge
+ * members into context scratch, from which their slice is copied.  Exactly len bytes are written.
+ * uoffset + len beyond index[members].uoffset, index[members].coffset beyond n or an index that
+ * is not monotone: DMX_ERR_ARG.  len == 0: DMX_OK, nothing launched.  Verification (DMX_VERIFY)
+ * and the ISIZE rule cover the touched members only.  Host synchronisations: 1.
+ *
+ * Not covered: preset dictionaries, multi-member gzip without BSIZE, graph capture; the host forms
+ * above do not go through these calls yet. */
+typedef struct dmx_bgzf_entry {
+    uint64_t coffset; /* the member's first byte in the BGZF file   */
+    uint64_t uoffset; /* its first byte in the plain (inflated) file */
+} dmx_bgzf_entry;
+int dmx_deflate_bgzf_device(dmx_ctx* ctx, const void* d_in, size_t n, int level, void* d_out, size_t cap,
+                            size_t* out_len, void* stream);
+int dmx_bgzf_index_device(dmx_ctx* ctx, const void* d_in, size_t n, dmx_bgzf_entry* entries, size_t entry_cap,
+                          size_t* members, uint64_t* plain_bytes, void* stream);
+int dmx_inflate_bgzf_device(dmx_ctx* ctx, const void* d_in, size_t n, uint32_t flags, void* d_out, size_t cap,
+                            size_t* out_len, void* stream);
+int dmx_inflate_bgzf_range_device(dmx_ctx* ctx, const void* d_in, size_t n, const dmx_bgzf_entry* index,
+                                  size_t members, uint64_t uoffset, size_t len, uint32_t flags, void* d_out,
+                                  void* stream);
 
 /* ---- instrumentation -------------------------------------------------------------------- */
 typedef struct dmx_stats {

@@ -19,11 +19,16 @@ profiles/batch_probe.json, which DESIGN quotes.
    dmx_inflate_gzip (host buffers, --loop-reps repetitions), and dmx_deflate_bgzf /
    dmx_inflate_bgzf of 256 MiB of text with their GB/s.
 
+5. BGZF in device memory (--bgzf-device, writes profiles/batch_probe_bgzf.json): 256 MiB of text,
+   level 2; dmx_deflate_bgzf / dmx_inflate_bgzf (host buffers) against dmx_deflate_bgzf_device /
+   dmx_inflate_bgzf_device (device buffers), alternated in one run, with the chain walk alone
+   (dmx_bgzf_index_device) and a 1 MiB ranged read beside them.
+
 Timing: synchronised host wall clock around each call (every call ends in a host
 synchronisation of its own), WARM warm-up repetitions, then REPS measured ones; the median is
 reported with the minimum beside it.
 
-  python tools/batch_probe.py [--reps 20] [--quick] [--dict | --framed [--loop-reps 20]]
+  python tools/batch_probe.py [--reps 20] [--quick] [--dict | --framed [--loop-reps 20] | --bgzf-device]
 """
 import argparse
 import ctypes
@@ -289,6 +294,60 @@ def bgzf_file(ctx, nbytes, reps):
     return row
 
 
+def bgzf_device_file(ctx, nbytes, reps):
+    """The host forms dmx_deflate_bgzf / dmx_inflate_bgzf against the device forms on the same
+    bytes, alternated in one run; the chain walk alone (dmx_bgzf_index_device) beside them."""
+    data = dmx.corpus("text", nbytes, offset=3 << 20)
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    bound = dmx.bgzf_bound(nbytes)
+    d_file = torch.empty(bound, dtype=torch.uint8, device="cuda")
+    d_out = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    d_part = torch.empty(min(1 << 20, nbytes // 4), dtype=torch.uint8, device="cuda")
+    f, flen, idx = [], [0], []
+
+    def deflate_host():
+        f[:] = [ctx.compress_bgzf(data, 2)]
+
+    def deflate_dev():
+        flen[0] = ctx.deflate_bgzf_device(d_in.data_ptr(), nbytes, 2, d_file.data_ptr(), bound)
+
+    def inflate_host():
+        assert len(ctx.decompress_bgzf(f[0], verify=True)) == nbytes
+
+    def inflate_dev():
+        assert ctx.inflate_bgzf_device(d_file.data_ptr(), flen[0], d_out.data_ptr(), nbytes, verify=True) == nbytes
+
+    def index_dev():
+        idx[:] = [ctx.bgzf_index_device(d_file.data_ptr(), flen[0])]
+
+    def range_dev():  # 1 MiB from the middle of the file
+        ctx.inflate_bgzf_range_device(d_file.data_ptr(), flen[0], idx[0], nbytes // 2 + 12345, d_part.numel(),
+                                      d_part.data_ptr())
+
+    dh, dd, ih, idv, ix, rg = alternate_all([deflate_host, deflate_dev, inflate_host, inflate_dev, index_dev, range_dev],
+                                            reps)
+    assert d_file[:flen[0]].cpu().numpy().tobytes() == f[0]
+    assert torch.equal(d_out, d_in)
+    assert torch.equal(d_part, d_in[nbytes // 2 + 12345:nbytes // 2 + 12345 + d_part.numel()])
+    # the chain kernels alone, by HIP events (the two read-backs between them included)
+    ctx.set_timing(True)
+    chain = []
+    for _ in range(WARM + reps):
+        index_dev()
+        chain.append(ctx.stats().ms_device_total)
+    ctx.set_timing(False)
+    row = {"kind": "text", "plain_bytes": nbytes, "file_bytes": flen[0], "members": int(idx[0].shape[0] - 1), "level": 2,
+           "deflate_bgzf_host": summary(dh), "deflate_bgzf_device": summary(dd),
+           "inflate_bgzf_host": summary(ih), "inflate_bgzf_device": summary(idv),
+           "bgzf_index_device": summary(ix), "bgzf_range_1MiB_device": summary(rg),
+           "chain_device_ms": summary(chain[WARM:]),
+           "device_beats_host_every_pass": {"deflate": all(d < h for d, h in zip(dd, dh)),
+                                            "inflate": all(d < h for d, h in zip(idv, ih))}}
+    for k in ("deflate_bgzf_host", "deflate_bgzf_device", "inflate_bgzf_host", "inflate_bgzf_device"):
+        row[k + "_gb_per_s"] = nbytes / (row[k]["median_ms"] * 1e6)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -296,14 +355,28 @@ def main():
     ap.add_argument("--dict", action="store_true", help="only the preset-dictionary shapes (part 3)")
     ap.add_argument("--framed", action="store_true", help="only the framed batch and BGZF shapes (part 4)")
     ap.add_argument("--loop-reps", type=int, default=20, help="--framed: repetitions of the single-buffer loops")
+    ap.add_argument("--bgzf-device", action="store_true", help="only BGZF in device memory against the host forms (part 5)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    name = "batch_probe_dict.json" if a.dict else "batch_probe_framed.json" if a.framed else "batch_probe.json"
+    name = ("batch_probe_dict.json" if a.dict else "batch_probe_framed.json" if a.framed else
+            "batch_probe_bgzf.json" if a.bgzf_device else "batch_probe.json")
     a.out = a.out or os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
         sys.exit("batch_probe: no GPU")
     ctx = dmx.Context()
     q = 8 if a.quick else 1
+    if a.bgzf_device:
+        result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
+                  "timing": "synchronised host wall clock per call, host and device forms alternated in one run, "
+                            "Python's garbage collector run between rounds; chain_device_ms: HIP events around "
+                            "dmx_bgzf_index_device's device work",
+                  "bgzf_device": [bgzf_device_file(ctx, (256 << 20) // q, a.reps)]}
+        print(json.dumps(result["bgzf_device"][0]), flush=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        ctx.close()
+        return
     if a.dict:
         result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
                   "timing": "synchronised host wall clock per call, with and without dictionary alternated",
