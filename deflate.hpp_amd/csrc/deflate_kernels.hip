@@ -115,6 +115,24 @@ constexpr bool DF_SKIP = DMX_DF_SKIP != 0;
 #ifndef DMX_DF_LITSKIP
 #define DMX_DF_LITSKIP 1
 #endif
+// Early load (32 KiB segments): the next segment of the workgroup is loaded into the match
+// rounds' table, dead once the rounds end, while the parse walk runs; the table and the byte
+// image are two buffers that swap roles on every segment, and the barriers at a segment's end
+// wait for LDS only (see deflate_segments).  0: the next segment is loaded into the image itself
+// after the token words, and the loop's closing barrier waits for it.  2: the early load with
+// the image and the table at fixed addresses: the loaded bytes are copied from the table to the
+// image, LDS to LDS, at the segment's end (the hot loops keep their constant LDS addresses)
+#ifndef DMX_DF_EARLYLOAD
+#define DMX_DF_EARLYLOAD 1
+#endif
+// (32 KiB segments only: two workgroups of the 16 KiB kernel share a CU, so one's wait for memory
+// passes behind the other's work, and the kernel has no register to spare for a buffer base)
+constexpr int df_early(int seg) { return seg >= 32768 ? DMX_DF_EARLYLOAD : 0; }
+// the early load is issued by the workgroup's upper eight waves, which the parse walk leaves
+// idle (0: by all sixteen, two loads each)
+#ifndef DMX_DF_EARLYHALF
+#define DMX_DF_EARLYHALF 1
+#endif
 // the front kernel counts the symbols (the emission kernel skips its histogram pass)
 #ifndef DMX_DF_HIST
 #define DMX_DF_HIST 0
@@ -125,6 +143,7 @@ constexpr bool DF_SKIP = DMX_DF_SKIP != 0;
 #ifndef DMX_DF_ADAPT
 #define DMX_DF_ADAPT 0
 #endif
+constexpr bool DF_EARLY_HALF = DMX_DF_EARLYHALF != 0 && !DMX_DF_ADAPT;  // (those chunks take every wave)
 // token-word count of a segment without any match (k_deflate_emit then reads its input's bytes)
 constexpr uint32_t EM_ALL_LITERALS = 0xFFFFFFFFu;
 
@@ -450,17 +469,33 @@ __device__ __forceinline__ RunPlan plan_run(uint32_t v, uint32_t r) {
 // ---------------------------------------------------------------------------------------
 // the segment kernel: 1024 threads (16 waves) per segment, one workgroup per CU
 // ---------------------------------------------------------------------------------------
+// The byte image, the candidates and the match rounds' table.  SWAP (df_early 1): the image and
+// the table are two buffers of one array that swap roles on every segment (see deflate_segments).
+template <int SEG, bool SWAP>
+struct DfBufs;
 template <int SEG>
-struct DfSmem {
+struct DfBufs<SEG, false> {
+    uint32_t data32[SEG / 4 + 32];  // + 128 B: matchlen4 reads up to 84 B past a match end
+    alignas(16) uint16_t cand[SEG + 8];
+    // the match rounds' HT pairs {head, first} (one ds_read_b64 per lookup)
+    alignas(16) uint32_t U[2 << df_hash_bits(SEG)];
+};
+template <int SEG>
+struct DfBufs<SEG, true> {
+    static constexpr int BW = SEG / 4 + 32;  // words per buffer: SEG bytes + 128 B (as data32)
+    static_assert((2 << df_hash_bits(SEG)) * 4 == SEG, "the table fills an image buffer's SEG bytes");
+    alignas(16) uint32_t buf[2][BW];
+    alignas(16) uint16_t cand[SEG + 8];
+};
+template <int SEG>
+struct DfSmem : DfBufs<SEG, df_early(SEG) == 1> {
+    static constexpr bool EARLY = df_early(SEG) != 0;  // the next segment loads during the parse walk
+    static constexpr bool SWAP = df_early(SEG) == 1;   // the image and the table swap roles
     static constexpr int NWALK = (SEG + DF_CHUNK - 1) / DF_CHUNK;
     static constexpr int NWALK_MAX = DMX_DF_ADAPT ? (SEG + DF_CHUNK / 2 - 1) / (DF_CHUNK / 2) : NWALK;
     static constexpr int HB = df_hash_bits(SEG);
     static constexpr int HT = 1 << HB;  // entries per hash table
     static constexpr int UW = 2 * HT;
-    uint32_t data32[SEG / 4 + 32];  // + 128 B: matchlen4 reads up to 84 B past a match end
-    alignas(16) uint16_t cand[SEG + 8];
-    // the match rounds' HT pairs {head, first} (one ds_read_b64 per lookup)
-    alignas(16) uint32_t U[UW];
     uint32_t mmap[SEG / 32];    // "a verified match of >= 3 starts here" (match rounds)
     uint32_t tokmap[SEG / 32];  // token-start bitmap (parse walk; chunks share boundary words)
     uint16_t lasttok[NWALK_MAX + 1];  // last token start of each parse chunk
@@ -469,12 +504,22 @@ struct DfSmem {
                       // 46: mismatch tag, 48..62: divisor-period tags
     uint32_t hist[DMX_DF_HIST ? 320 : 1];  // the segment's symbol counts (see deflate_tok_stride)
 };
+static_assert(sizeof(DfSmem<32768>) <= 160 * 1024, "the front kernel's LDS fits a CU's 160 KiB");
+
+// A barrier between phases that hand over LDS only: it waits for the wave's LDS accesses and not
+// for its stores to HBM (the token words and the phase stamps, which a later kernel reads).  The
+// asm statements keep the compiler from moving an LDS access across the barrier.
+__device__ __forceinline__ void df_lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
 
 // Persistent workgroups: the next segment of this workgroup (seg + gridDim.x) is loaded straight
-// into the LDS byte image (global_load_lds, no registers) once the current segment's bytes are
-// dead -- after its token words are written -- so its memory latency passes during the stores
-// and the loop's bookkeeping.  The loop's closing
-// __syncthreads waits for it (an LDS-DMA load counts on vmcnt).
+// into LDS (global_load_lds, no registers).  Early load: into the match rounds' table, issued
+// before the parse walk; the barrier after the walk waits for it (an LDS-DMA load counts on
+// vmcnt).  Otherwise: into the byte image once the current segment's bytes are dead -- after its
+// token words are written -- and the loop's closing __syncthreads waits for it.
 // Where segment `seg` of SEG bytes lies.  One stream (BATCH false): computed from A.in / A.n.
 // A batch: read from the segment table (A.btab), whose entries span several buffers.
 // DICT (a batch with a preset dictionary): also the dictionary bytes that precede the segment's
@@ -514,7 +559,7 @@ __device__ __forceinline__ DfSegAddr df_seg_addr(const DeflateArgs& A, uint64_t 
 }
 
 template <int SEG, bool BATCH, bool DICT = false>
-__device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t seg, DfSmem<SEG>& S) {
+__device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t seg, uint32_t* image) {
     bool go;
     const uint8_t* nsrc;
     if constexpr (BATCH) {
@@ -537,11 +582,46 @@ __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t 
         const int t = df_tid();
         const uint4* src = reinterpret_cast<const uint4*>(nsrc) + t;
         // one wave-instruction writes 64 x 16 B contiguously from a wave-uniform LDS base
-        uint4* dst = reinterpret_cast<uint4*>(S.data32) + (t & ~63);
+        uint4* dst = reinterpret_cast<uint4*>(image) + (t & ~63);
+        if constexpr (df_early(SEG) != 0 && DF_EARLY_HALF) {
+            // (the asm form below) Waves 8..15 issue all of it, four loads each: the parse walk
+            // that follows occupies waves 0..7 only (NWALK quads), which then start at once
+            static_assert(4 * DfSmem<SEG>::NWALK_MAX <= DF_NT / 2, "the walk leaves the upper waves idle");
+            if (t >= DF_NT / 2) {
+                const uint32_t base = __builtin_amdgcn_readfirstlane(
+                    (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(dst - DF_NT / 2));
 #pragma unroll
-        for (int k = 0; k < SEG / (16 * DF_NT); k++)
-            __builtin_amdgcn_global_load_lds(src + k * DF_NT, (__attribute__((address_space(3))) void*)(dst + k * DF_NT),
-                                             16, 0, 0);
+                for (int k = 0; k < SEG / (8 * DF_NT); k++) {
+                    uint32_t keep;
+                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                                 : "=&s"(keep)
+                                 : "v"(src - DF_NT / 2 + k * (DF_NT / 2)), "s"(base + (uint32_t)(k * DF_NT * 8))
+                                 : "memory");
+                }
+            }
+        } else if constexpr (df_early(SEG) != 0) {
+            // As an asm statement: the compiler counts a global_load_lds it knows of as a pending
+            // LDS write and waits vmcnt(0) before the wave's next LDS store or atomic -- the parse
+            // walk's first token bit.  The caller waits for these loads itself.  (M0, the LDS
+            // base of the load, is the compiler's: saved and restored in the same statement.)
+            const uint32_t base = __builtin_amdgcn_readfirstlane(
+                (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)dst);
+#pragma unroll
+            for (int k = 0; k < SEG / (16 * DF_NT); k++) {
+                uint32_t keep;
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                             "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep)
+                             : "v"(src + k * DF_NT), "s"(base + (uint32_t)(k * DF_NT * 16))
+                             : "memory");
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < SEG / (16 * DF_NT); k++)
+                __builtin_amdgcn_global_load_lds(src + k * DF_NT, (__attribute__((address_space(3))) void*)(dst + k * DF_NT),
+                                                 16, 0, 0);
+        }
     }
     return go;
 }
@@ -586,7 +666,17 @@ __device__ __forceinline__ void df_load_at(uint8_t* dbytes, uint32_t off, const 
 // without DICT (and for the later segments of a buffer) D = 0 and nb = the segment's bytes.
 template <int SEG, bool L3, bool BATCH, bool DICT>
 __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG>& S, uint64_t seg,
-                                                bool& staged) {
+                                                uint32_t& staged, [[maybe_unused]] uint32_t iw) {
+    constexpr bool EARLY = DfSmem<SEG>::EARLY, SWAP = DfSmem<SEG>::SWAP;
+    // the byte image and the match rounds' table (SWAP: the buffer at word iw and the other one)
+    uint32_t *data32, *U;
+    if constexpr (SWAP) {
+        data32 = &S.buf[0][0] + iw;
+        U = &S.buf[0][0] + ((uint32_t)DfSmem<SEG>::BW - iw);
+    } else {
+        data32 = S.data32;
+        U = S.U;
+    }
     [[maybe_unused]] constexpr int NWALK = DfSmem<SEG>::NWALK;
     constexpr int HT = DfSmem<SEG>::HT;
     constexpr int NMAP = SEG / 32;
@@ -595,7 +685,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
     const uint32_t D = DICT ? sa.dlen : 0u;
     const uint32_t nb = D + sa.nb;
     constexpr int level = L3 ? 3 : 2;  // (the front kernel runs at levels 2 and 3 only)
-    uint8_t* const dbytes = reinterpret_cast<uint8_t*>(S.data32);
+    uint8_t* const dbytes = reinterpret_cast<uint8_t*>(data32);
     // (32 KiB segments only: the 16 KiB kernel sits at its 64-register limit, and with this code
     // in it the compiler spills its kernel arguments to scratch)
     constexpr bool TERMRUN = DF_SKIP && !L3 && SEG >= 32768 && DMX_DF_TERMRUN;
@@ -614,7 +704,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             df_load_at(dbytes, D, src, nb - D, t);
         } else if ((((uintptr_t)src) & 15) == 0) {
             const uint4* s4 = reinterpret_cast<const uint4*>(src);
-            uint4* d4 = reinterpret_cast<uint4*>(S.data32);
+            uint4* d4 = reinterpret_cast<uint4*>(data32);
             for (uint32_t i = t; i < nvec; i += DF_NT) d4[i] = s4[i];
             for (uint32_t i = nvec * 16 + t; i < nb; i += DF_NT) dbytes[i] = src[i];
         } else {
@@ -628,12 +718,16 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         if (RUNBACK && t == 2) S.sh[43] = 0;  // the run's last mismatch in the round before it
         if (t >= 48 && t < 63) S.sh[t] = 0;  // its divisor-period tags
         if (DMX_DF_HIST && t < 320) S.hist[t] = 0;
-        if (level >= 2)
-            for (int i = t; i < 2 * HT; i += DF_NT) S.U[i] = 0;
+        if (level >= 2 && EARLY) {  // (SWAP: the previous segment's image, dead since its last barrier)
+            uint4* const u4 = reinterpret_cast<uint4*>(U);
+            for (int i = t; i < 2 * HT / 4; i += DF_NT) u4[i] = make_uint4(0, 0, 0, 0);
+        } else if (level >= 2)
+            for (int i = t; i < 2 * HT; i += DF_NT) U[i] = 0;
     }
-    __syncthreads();
+    if constexpr (EARLY) df_lds_barrier();
+    else __syncthreads();
     DMX_PHASE(A.dbg, seg, 1);
-    staged = false;
+    staged = 0;
 
     if (level != 0) {
         bool any_skip = false;  // (uniform) the run continuation took a round of this segment
@@ -667,7 +761,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             // lookup must not see later positions of its own round); the first occurrence in a
             // round is resolved by the round number in the entry.
             constexpr uint32_t HB = DfSmem<SEG>::HB;
-            const uint2* const tab = reinterpret_cast<const uint2*>(S.U);
+            const uint2* const tab = reinterpret_cast<const uint2*>(U);
             uint32_t* const cand32 = reinterpret_cast<uint32_t*>(S.cand);
             uint32_t ph0 = 0, ph1 = 0, pp0 = 0, pf0 = 0, pf1 = 0;  // previous round: hashes, p0, fp16s
             bool pok0 = false, pok1 = false;
@@ -684,7 +778,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     uint32_t h0 = NOH, h1 = NOH, fa0 = 0, fa1 = 0, k0 = 0, k1 = 1;
                     bool ok0 = false, ok1 = false;
                     if (act) {
-                        const uint32_t wa = S.data32[p0 >> 2], wb = S.data32[(p0 >> 2) + 1];
+                        const uint32_t wa = data32[p0 >> 2], wb = data32[(p0 >> 2) + 1];
                         k0 = __builtin_amdgcn_alignbyte(wb, wa, p0 & 3);
                         k1 = __builtin_amdgcn_alignbyte(wb, wa, (p0 & 3) + 1);
                         const uint32_t prod0 = k0 * 0x1E35A7BDu, prod1 = k1 * 0x1E35A7BDu;
@@ -695,8 +789,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         fa0 = (prod0 >> (32 - HB - 16)) & 0xFFFFu;
                         fa1 = (prod1 >> (32 - HB - 16)) & 0xFFFFu;
                         const uint32_t hn = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)(pok0 ? ph0 : NOH), 0x101, 0xF, 0xF, false);
-                        if (pok0 && ph0 != (pok1 ? ph1 : NOH)) atomicMax(&S.U[2 * ph0], ((pp0 + 1) << 16) | pf0);
-                        if (pok1 && ph1 != hn) atomicMax(&S.U[2 * ph1], ((pp0 + 2) << 16) | pf1);
+                        if (pok0 && ph0 != (pok1 ? ph1 : NOH)) atomicMax(&U[2 * ph0], ((pp0 + 1) << 16) | pf0);
+                        if (pok1 && ph1 != hn) atomicMax(&U[2 * ph1], ((pp0 + 2) << 16) | pf1);
                     }
                     __syncthreads();
                     if (act) {
@@ -773,7 +867,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         uint32_t dlr = 0;  // (issued first: its latency overlaps the data words')
                         if (SKIP && pend) dlr = S.sh[44];
                         const uint32_t i0 = p0 >> 2, sh = p0 & 3;  // sh = 0 or 2
-                        const uint32_t wa = S.data32[i0], wb = S.data32[i0 + 1];
+                        const uint32_t wa = data32[i0], wb = data32[i0 + 1];
                         const uint32_t k0 = __builtin_amdgcn_alignbyte(wb, wa, sh);
                         const uint32_t k1 = __builtin_amdgcn_alignbyte(wb, wa, sh + 1);
                         const uint32_t prod0 = k0 * 0x1E35A7BDu;
@@ -788,15 +882,15 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         const uint32_t hl = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)h1, 0x111, 0xF, 0xF, false);
                         const uint32_t rtag = rr << (32 - TAGB);
                         if (ok0 && h0 != hl)
-                            atomicMax(&S.U[2 * h0 + 1], rtag | ((0x7FFFu - p0) << FPB) | (fa0 >> (16 - FPB)));
+                            atomicMax(&U[2 * h0 + 1], rtag | ((0x7FFFu - p0) << FPB) | (fa0 >> (16 - FPB)));
                         if (ok1 && h1 != h0)
-                            atomicMax(&S.U[2 * h1 + 1], rtag | ((0x7FFFu - p1) << FPB) | (fa1 >> (16 - FPB)));
+                            atomicMax(&U[2 * h1 + 1], rtag | ((0x7FFFu - p1) << FPB) | (fa1 >> (16 - FPB)));
                         // latest occurrence, for the previous round's positions: its p0 needs no update
                         // when its p0 + 1 has the hash, p0 + 1 none when p0 + 2 (the next lane's) has it
                         const uint32_t hn = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)(prev.ok0 ? prev.h0 : NOH), 0x101, 0xF, 0xF, false);
                         if (prev.ok0 && prev.h0 != (prev.ok1 ? prev.h1 : NOH))
-                            atomicMax(&S.U[2 * prev.h0], ((prev.p0 + 1) << 16) | prev.f0);
-                        if (prev.ok1 && prev.h1 != hn) atomicMax(&S.U[2 * prev.h1], ((prev.p0 + 2) << 16) | prev.f1);
+                            atomicMax(&U[2 * prev.h0], ((prev.p0 + 1) << 16) | prev.f0);
+                        if (prev.ok1 && prev.h1 != hn) atomicMax(&U[2 * prev.h1], ((prev.p0 + 2) << 16) | prev.f1);
                         bool tested = false;
                         if (SKIP && pend) {
                             pend = false;
@@ -816,7 +910,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                                     const uint32_t ki = (uint32_t)t >> 6, k = ki + 2, bq = r0 + 4 * ((uint32_t)t & 63);
                                     if (ki < 15 && dl % k == 0 && bq + 4 <= nb) {
                                         const uint32_t dk = dl / k, ia = (bq - dk) >> 2, sk = (bq - dk) & 3;
-                                        if (S.data32[bq >> 2] != __builtin_amdgcn_alignbyte(S.data32[ia + 1], S.data32[ia], sk))
+                                        if (data32[bq >> 2] != __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sk))
                                             atomicMax(&S.sh[48 + ki], rr + 1);
                                     }
                                 }
@@ -836,8 +930,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                                     const uint32_t bq = r0 + 4 * ((uint32_t)t + DF_NT * j);
                                     if (bq < nb) {
                                         const uint32_t ia = (bq - dl) >> 2;
-                                        const uint32_t df = S.data32[bq >> 2] ^
-                                                            __builtin_amdgcn_alignbyte(S.data32[ia + 1], S.data32[ia], sa);
+                                        const uint32_t df = data32[bq >> 2] ^
+                                                            __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sa);
                                         mm = df ? bq + ((uint32_t)__builtin_ctz(df) >> 3) : mm;
                                     }
                                 }
@@ -962,15 +1056,15 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     // test, widened): one word compare per link, the full length only for the
                     // links that pass.
                     auto ml = [&](uint32_t a, uint32_t b, uint32_t m) {
-                        return DF_L3_U >= 2 ? matchlen_u(S.data32, a, b, m) : matchlen(S.data32, a, b, m);
+                        return DF_L3_U >= 2 ? matchlen_u(data32, a, b, m) : matchlen(data32, a, b, m);
                     };
                     auto rd = [&](uint32_t a) {
-                        return DF_L3_U >= 1 ? lds_rd32u(S.data32, a) : ld32u(S.data32, a);
+                        return DF_L3_U >= 1 ? lds_rd32u(data32, a) : ld32u(data32, a);
                     };
                     uint32_t q = p - d0;
                     // (the first link with aligned words: neighbouring lanes read neighbouring
                     // bytes here, which unaligned 8-byte reads serve slower -- repeat +46 %)
-                    uint32_t bl = DF_L3_U >= 3 ? matchlen(S.data32, p, q, min(maxl, DF_L3_LONG))
+                    uint32_t bl = DF_L3_U >= 3 ? matchlen(data32, p, q, min(maxl, DF_L3_LONG))
                                                : ml(p, q, min(maxl, DF_L3_LONG));
                     if (bl >= 3) bd = d0;
                     else bl = 2;  // (a fingerprint collision: no match yet)
@@ -1038,8 +1132,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     const uint32_t bq = run_lo - RP + 4 * (uint32_t)t;
                     if ((uint32_t)t < RP / 4 && bq >= run_d) {
                         const uint32_t ia = (bq - run_d) >> 2;
-                        const uint32_t df = S.data32[bq >> 2] ^
-                                            __builtin_amdgcn_alignbyte(S.data32[ia + 1], S.data32[ia], (run_lo - run_d) & 3);
+                        const uint32_t df = data32[bq >> 2] ^
+                                            __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], (run_lo - run_d) & 3);
                         if (df) atomicMax(&S.sh[43], ((run_lo / RP + 1) << 16) | (bq + 4 - ((uint32_t)__builtin_clz(df) >> 3)));
                     }
                 }
@@ -1056,6 +1150,9 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             }
         }
         DMX_PHASE(A.dbg, seg, 2);
+        // Early load: the table is dead (every wave has passed its last read of it), so the next
+        // segment's bytes travel into it during the walk; the barrier after the walk waits for them
+        if constexpr (EARLY) staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, U);
 
         // ---- parse walk: one DF_CHUNK-byte chunk per quad of lanes (the four walk in step and
         //      share the match-length compares, matchlen4); jumps over literal runs with the
@@ -1092,9 +1189,9 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             // matchlen4 of q against q - d; the length itself where it is known (a select on
             // the compared length: a known match compares nothing)
             auto len_at = [&](uint32_t q, uint32_t d, uint32_t maxl) -> uint32_t {
-                if (!KNOWN) return matchlen4(S.data32, q, q - d, maxl, sub);
+                if (!KNOWN) return matchlen4(data32, q, q - d, maxl, sub);
                 const bool kn = known_len(q, d);
-                const uint32_t L = matchlen4(S.data32, q, q - d, kn ? 0u : maxl, sub);
+                const uint32_t L = matchlen4(data32, q, q - d, kn ? 0u : maxl, sub);
                 return kn ? maxl : L;
             };
             auto full_len = [&](uint32_t q) -> uint32_t {  // < 3 only on a fingerprint collision
@@ -1172,8 +1269,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                             uint32_t x = 0;
 #pragma unroll
                             for (int k = 0; k < 4; k++)
-                                x |= __builtin_amdgcn_alignbyte(S.data32[ip + k + 1], S.data32[ip + k], sp) ^
-                                     __builtin_amdgcn_alignbyte(S.data32[iq + k + 1], S.data32[iq + k], sq);
+                                x |= __builtin_amdgcn_alignbyte(data32[ip + k + 1], data32[ip + k], sp) ^
+                                     __builtin_amdgcn_alignbyte(data32[iq + k + 1], data32[iq + k], sq);
                             pass = x == 0;
                         }
                         const int qb = lane_id() & ~3;
@@ -1192,7 +1289,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         uint32_t k = 1;
 #pragma unroll
                         for (uint32_t q = 2; q <= 8; q++) k = (c % q == 0) ? q : k;
-                        if (k > 1 && matchlen4(S.data32, p, p - c / k, ml, sub) >= L) best = c / k;
+                        if (k > 1 && matchlen4(data32, p, p - c / k, ml, sub) >= L) best = c / k;
                     }
                     if (DF_SKIP && best == c) {
                         // divisors c / k of the candidate, k <= 16 (the run-continuation rounds give
@@ -1213,8 +1310,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                             uint32_t x = 0;
 #pragma unroll
                             for (int j = 0; j < 4; j++)
-                                x |= __builtin_amdgcn_alignbyte(S.data32[ip + j + 1], S.data32[ip + j], sp) ^
-                                     __builtin_amdgcn_alignbyte(S.data32[iq + j + 1], S.data32[iq + j], sq);
+                                x |= __builtin_amdgcn_alignbyte(data32[ip + j + 1], data32[ip + j], sp) ^
+                                     __builtin_amdgcn_alignbyte(data32[iq + j + 1], data32[iq + j], sq);
                             pass = x == 0;
                         }
                         const int qb = lane_id() & ~3;
@@ -1245,6 +1342,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             } else
                 parse_walk(std::false_type{});
         }
+        if constexpr (EARLY) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the early load has landed
         __syncthreads();
         DMX_PHASE(A.dbg, seg, 3);
 
@@ -1264,7 +1362,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 const uint32_t s0 = S.lasttok[c], d0 = S.cand[s0], L0 = S.cand[s0 + 1];
                 const uint32_t sn = S.lasttok[c + 1];  // the extension ends before it
                 if (d0 != 0 && s0 + L0 == hb && L0 < 258 && sn >= hb + 2) {
-                    const uint32_t Lx = matchlen4(S.data32, s0, s0 - d0, min(258u, sn - 1 - s0), sub);
+                    const uint32_t Lx = matchlen4(data32, s0, s0 - d0, min(258u, sn - 1 - s0), sub);
                     const uint32_t e = s0 + Lx;  // < sn
                     uint32_t q = 0;
                     if (Lx > L0) {  // the next chunk's token at or before e (before sn)
@@ -1359,7 +1457,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 for (uint32_t i = D + t; i < nb; i += DF_NT) atomicAdd(&S.hist[dbytes[i]], 1u);
             } else if (DMX_DF_HIST)  // the literal histogram, four bytes per word
                 for (uint32_t i = t; 4 * i < nb; i += DF_NT) {
-                    const uint32_t x = S.data32[i];
+                    const uint32_t x = data32[i];
 #pragma unroll
                     for (uint32_t b = 0; b < 4; b++)
                         if (4 * i + b < nb) atomicAdd(&S.hist[(x >> (8 * b)) & 0xFFu], 1u);
@@ -1376,7 +1474,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         lit = 0;
                         emit(0x80000000u | ((uint32_t)(S.cand[p + 1] - 3) << 16) | (d - 1));
                     } else {
-                        lit |= (uint32_t)data_byte(S.data32, p) << (8 * nl);
+                        lit |= (uint32_t)data_byte(data32, p) << (8 * nl);
                         if (++nl == 3) {
                             emit(lit | (3u << 24));
                             nl = 0;
@@ -1409,25 +1507,49 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             if (t == 0) A.ntok[seg] = wtot;
         }
         DMX_PHASE(A.dbg, seg, 11);
-        __syncthreads();  // every read of the segment's bytes is done
+        // every read of the segment's bytes is done (SWAP: nothing below writes LDS, and the
+        // loop's closing barrier stands for this one)
+        if (EARLY && !SWAP) df_lds_barrier();
+        else if (!EARLY || DMX_DF_HIST) __syncthreads();
+        if (EARLY && !SWAP && staged) {  // the next segment's bytes: from the table to the image
+            const uint4* const u4 = reinterpret_cast<const uint4*>(U);
+            uint4* const d4 = reinterpret_cast<uint4*>(data32);
+#pragma unroll
+            for (int k = 0; k < SEG / (16 * DF_NT); k++) d4[t + k * DF_NT] = u4[t + k * DF_NT];
+        }
         if (DMX_DF_HIST && t < (int)kDeflateHistWords)
             A.tok[seg * (uint64_t)A.tok_stride + A.tok_stride - kDeflateHistWords + t] = S.hist[2 * t] | (S.hist[2 * t + 1] << 16);
-        staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, S);
+        if constexpr (!EARLY) staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, data32);
         DMX_PHASE(A.dbg, seg, 10);
     }
 }
 
-// The 32 KiB kernel is limited to one workgroup per CU by its LDS (~146 KiB), so the compiler may
-// use up to 128 registers; the 16 KiB one fits two workgroups per CU (80 KiB each) only at <= 64
+// The 32 KiB kernel is limited to one workgroup per CU by its LDS (137 KiB), so the compiler may
+// use up to 128 registers; the 16 KiB one fits two workgroups per CU (69 KiB each) only at <= 64
 // registers per lane, which amdgpu_waves_per_eu(8) asks for.
 // Persistent workgroups (as many as fit the GPU at once): workgroup b compresses segments
 // b, b + G, b + 2G, ... and loads each next segment while it works on the current one.
+// Early load with swapping buffers (DfSmem::SWAP): the image and the table are the two buffers of S.buf, and they
+// swap roles on EVERY segment, staged or not (a workgroup-uniform base offset): the next
+// segment's bytes go into the current table, which is the next image.  A segment that was not
+// staged (an unaligned source, a short or a dictionary segment) loads into its image buffer at
+// its start.  The 128 bytes after each buffer's first SEG are zeroed once: the table never
+// writes there and a staged load brings exactly SEG bytes.
 template <int SEG, bool L3, bool BATCH, bool DICT>
 __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SEG>& S) {
-    bool staged = false;  // S.data32 already holds the segment's bytes
+    constexpr bool EARLY = DfSmem<SEG>::EARLY, SWAP = DfSmem<SEG>::SWAP;
+    uint32_t staged = 0;  // the image already holds the segment's bytes
+    uint32_t iw = 0;      // (SWAP) the image's first word in S.buf: 0 or BW
+    if constexpr (SWAP) {
+        const int t = df_tid();
+        if (t < 64) S.buf[t >> 5][SEG / 4 + (t & 31)] = 0;  // (the first segment's barrier covers it)
+    }
     for (uint64_t seg = blockIdx.x; seg < A.nseg; seg += gridDim.x) {
-        deflate_segment<SEG, L3, BATCH, DICT>(A, S, seg, staged);
-        __syncthreads();  // the next segment reuses the LDS (and its prefetch has landed)
+        deflate_segment<SEG, L3, BATCH, DICT>(A, S, seg, staged, iw);
+        // the next segment reuses the LDS (not EARLY: and its prefetch has landed)
+        if constexpr (EARLY) df_lds_barrier();
+        else __syncthreads();
+        if constexpr (SWAP) iw = (uint32_t)DfSmem<SEG>::BW - iw;
     }
 }
 // BATCH: the segments come from the batch's segment table (df_seg_addr); the default
@@ -2262,10 +2384,8 @@ __global__ __launch_bounds__(256) void k_compact_batch(DeflateArgs A) {
     A.bres[b] = r;
 }
 
-hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st,
-                          hipEvent_t ev_main0, hipEvent_t ev_main1, bool dict) {
-    if (dict && (!A.btab || seg_bytes != 32768)) return hipErrorInvalidValue;
-    // persistent grid: the workgroups that fit at once (CUs x workgroups per CU)
+// the front kernel's persistent grid: the workgroups that fit at once (CUs x workgroups per CU)
+uint64_t deflate_front_fit(uint32_t seg_bytes) {
     int dev = 0, ncu = 0, per = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -2273,7 +2393,13 @@ hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t 
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_deflate_segments<32768, false>, DF_NT, 0);
     else
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_deflate_segments16<false>, DF_NT, 0);
-    const uint64_t fit = (uint64_t)max(ncu, 1) * (uint64_t)max(per, 1);
+    return (uint64_t)max(ncu, 1) * (uint64_t)max(per, 1);
+}
+
+hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st,
+                          hipEvent_t ev_main0, hipEvent_t ev_main1, bool dict) {
+    if (dict && (!A.btab || seg_bytes != 32768)) return hipErrorInvalidValue;
+    const uint64_t fit = deflate_front_fit(seg_bytes);
     const uint32_t grid = (uint32_t)std::min<uint64_t>(A.nseg, fit);  // host min(int, int) would truncate
     if (ev_main0) (void)hipEventRecord(ev_main0, st);
     if (A.btab) {  // a batch: the same stages over the segment table, k_compact_batch at the end

@@ -131,7 +131,8 @@ struct Scal {  // small device-side scalars, one allocation
 // DMX_PHASES=<file>: kernels record s_memtime per phase and segment; the host appends one line
 // "<kernel> <nsegs> <mean cycles of phase k - phase k-1 ...>" per call (developer profiling).
 uint64_t* phase_buf(dmx_ctx* c, uint64_t nidx);
-void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st);
+// stride (deflate): the front kernel's grid, for the interval between a workgroup's segments
+void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st, uint64_t stride = 0);
 
 void begin_timing(dmx_ctx* c, hipStream_t st);
 void end_timing(dmx_ctx* c, hipStream_t st);

@@ -43,7 +43,7 @@ uint64_t* phase_buf(dmx_ctx* c, uint64_t nidx) {
     (void)hipMemset(c->dbg.p, 0, nidx * kPhaseSlots * 8);
     return c->dbg.as<uint64_t>();
 }
-void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st) {
+void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st, uint64_t stride) {
     if (!(c->diag & DIAG_PHASES) || !c->dbg.p) return;
     const char* path = diag_env().phases_path.c_str();
     std::vector<uint64_t> h(nidx * kPhaseSlots);
@@ -84,6 +84,22 @@ void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st) {
                 if (r[k] && r[0] && r[k] >= r[0]) { a += (double)(r[k] - r[0]); m++; }
             }
             if (m) std::fprintf(f, " t%d=%.0f", k, a / m);
+        }
+        // Persistent workgroups (stride = the grid): what no phase counts, between a segment and
+        // the workgroup's next one.  gap: from the token words' end (slot 11) to the next
+        // segment's loaded image (its slot 1); gap0: from the segment's last stamp (slot 10) to
+        // the next one's first (slot 0), the loop's closing barrier
+        if (stride && stride < nidx) {
+            double g = 0, g0 = 0;
+            uint64_t m = 0;
+            for (uint64_t i = 0; i + stride < nidx; i++) {
+                const uint64_t *r = &h[i * kPhaseSlots], *q = &h[(i + stride) * kPhaseSlots];
+                if (!r[11] || !r[10] || q[1] < r[11] || q[0] < r[10]) continue;
+                g += (double)(q[1] - r[11]);
+                g0 += (double)(q[0] - r[10]);
+                m++;
+            }
+            if (m) std::fprintf(f, " gap=%.0f gap0=%.0f", g / m, g0 / m);
         }
     }
     if (inf)
@@ -177,7 +193,7 @@ int deflate_device_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, int level, 
     HIPCHK(hipEventRecord(c->ev_df, st));
     c->df_pending = true;
     if (async) return DMX_OK;
-    if (A.dbg) phase_dump(c, "deflate", nseg, st);
+    if (A.dbg) phase_dump(c, "deflate", nseg, st, c->seg == 65536 ? 0 : std::min<uint64_t>(nseg, deflate_front_fit(c->seg)));
     uint64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, A.total, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

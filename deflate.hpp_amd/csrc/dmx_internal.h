@@ -66,6 +66,9 @@ constexpr uint32_t deflate_tok_stride(uint32_t seg) { return seg / 2 + 1024 + 64
 // dict: the batch's segment table carries a preset dictionary (32 KiB segments, levels 2-3)
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, hipEvent_t ev0,
                           hipEvent_t ev1, bool dict = false);
+// the front kernel's persistent workgroups that fit the GPU at once: workgroup b takes the
+// segments b, b + grid, ... with grid = min(segments, this)
+uint64_t deflate_front_fit(uint32_t seg_bytes);
 
 // InflateArgs::flags bit (internal): the stream is a piece of a larger stream (multi-GPU
 // scatter): a back-reference before its first byte is an error, not the stream-start no-op.

@@ -27,3 +27,20 @@ for kind in os.environ.get("DMX_KINDS", "repeat,text,zeros").split(","):
         with open(out, "a") as f:
             f.write(f"# {kind} L{lvl} ratio {n/clen:.3f} deflate_kernel_ms {kd:.3f} inflate_kernel_ms {ki:.3f} ok {olen == n and torch.equal(d_o[:n], d_in)}\n")
 print(open(out).read())
+
+# The front kernel's phases per corpus, cycles per segment from wave 0's stamps (the rows of
+# profiles/r0N_variants.txt), and what no phase counts: the interval from a segment's token words
+# (stamp 11) to the loaded image of the same workgroup's next segment (stamp 1 of seg + grid).
+COLS = "load | round 0 | round 1 | to stamp 14 | bitmap + fill | parse walk | fix-up + token ranges | token words | prefetch | total | 11 -> next 1 | 10 -> next 0"
+print("# " + COLS)
+kind = None
+for line in open(out):
+    if line.startswith("# corpus "):
+        kind = line.split()[2]
+    elif line.startswith("deflate ") and kind:
+        v = dict(kv.split("=") for kv in line.split()[2:] if "=" in kv)
+        t = lambda k: float(v.get("t%d" % k, 0))  # noqa: E731
+        row = [t(1), t(12) - t(1), t(13) - t(12), t(14) - t(13), t(2) - t(14), t(3) - t(2), t(15) - t(3),
+               t(11) - t(15), t(10) - t(11), t(10), float(v.get("gap", 0)), float(v.get("gap0", 0))]
+        print(f"{kind}: {os.environ.get('DMX_TAG', '')}  " + " | ".join("%.0f" % x for x in row))
+        kind = None
