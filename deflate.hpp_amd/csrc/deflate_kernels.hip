@@ -2,7 +2,7 @@
 //
 // One 1024-thread workgroup (16 waves) compresses one independent segment (32 KiB, or 16 KiB)
 // entirely out of LDS, the way the reference compresses one 32 KiB chunk with a fresh LZ77 state
-// (realCompress, /root/reference/include/deflate.hpp:680-752):
+// (realCompress, the reference's include/deflate.hpp:680-752):
 //
 //   load (16 B/lane coalesced)  -> LDS byte image of the segment
 //   match rounds                -> a fingerprinted {latest, first-in-round} hash table in LDS,
@@ -36,10 +36,7 @@
 namespace dmx {
 
 constexpr int DF_NT = 1024;    // threads per workgroup (16 waves)
-#ifndef DMX_DF_CHUNK
-#define DMX_DF_CHUNK 258
-#endif
-constexpr int DF_CHUNK = DMX_DF_CHUNK;  // bytes per parse lane: one maximal match per chunk, and not a
+constexpr int DF_CHUNK = 258;  // bytes per parse lane: one maximal match per chunk, and not a
                                // multiple of 256, so the lanes' chunk starts spread over the LDS
                                // banks (at 256 every lane of a wave hit one bank per matchlen read)
 constexpr int df_hash_bits(int seg) {  // hash bits of each of the two match tables: 11 at 16 KiB
@@ -48,102 +45,32 @@ constexpr int df_hash_bits(int seg) {  // hash bits of each of the two match tab
 // Code-length limits of the emitted lit/len and distance codes.  RFC 1951 allows 15; 9 and 6
 // keep every code inside the one-level lookup tables of the lane decoder
 // (inflate_lanes.hip: 512 + 64 entries per segment in LDS) at < 1% ratio cost.
-#ifndef DMX_LIT_MAXBITS
-#define DMX_LIT_MAXBITS 9
-#define DMX_DIST_MAXBITS 6
-#endif
-constexpr int DF_LIT_MAXBITS = DMX_LIT_MAXBITS;
-constexpr int DF_DIST_MAXBITS = DMX_DIST_MAXBITS;
-#ifndef DMX_L3_DEPTH
-#define DMX_L3_DEPTH 16
-#endif
-constexpr int DF_L3_DEPTH = DMX_L3_DEPTH;  // level 3: candidate-chain links searched per position
-#ifndef DMX_L3_LONG
-#define DMX_L3_LONG 16
-#endif
-constexpr uint32_t DF_L3_LONG = DMX_L3_LONG;  // level 3: a first link this long ends the chain search
-#ifndef DMX_L3_ROUND
-#define DMX_L3_ROUND 128
-#endif
-constexpr uint32_t DF_L3_ROUND = DMX_L3_ROUND;  // level 3: positions per link-building round
-// Level 3 links: the level-2 candidates (first occurrence in the round, else the latest before
-// it) by default; 1 = the single-wave link rounds of DF_L3_ROUND positions (latest occurrence
-// before the position's round), which cannot see an occurrence inside the same round.
-#ifndef DMX_L3_LINK_ROUNDS
-#define DMX_L3_LINK_ROUNDS 0
-#endif
-constexpr bool DF_L3_LINK_ROUNDS = DMX_L3_LINK_ROUNDS != 0;
+constexpr int DF_LIT_MAXBITS = 9;
+constexpr int DF_DIST_MAXBITS = 6;
+constexpr int DF_L3_DEPTH = 16;  // level 3: candidate-chain links searched per position
+constexpr uint32_t DF_L3_LONG = 16;  // level 3: a first link this long ends the chain search
 // Level 3: positions per match round (the level-2 rounds take 2 * DF_NT = 2048)
-#ifndef DMX_L3_U
-#define DMX_L3_U 3
-#endif
-// level 3's chain search: 1 = the tail test as one unaligned 4-byte LDS read, 2 = also the match
-// lengths by unaligned 8-byte reads, 3 = those but the first link's length by aligned words
-// (0 = aligned words and alignbyte throughout)
-[[maybe_unused]] constexpr int DF_L3_U = DMX_L3_U;
-#ifndef DMX_L3_RP
-#define DMX_L3_RP 512
-#endif
-constexpr uint32_t DF_L3_RP = DMX_L3_RP;
-// level 2: run-continuation test of the match rounds (see run_rounds).  Measured on 1 GiB (ms):
+constexpr uint32_t DF_L3_RP = 512;
+// Level 2's match rounds test whether a run continues (see run_rounds).  Measured on 1 GiB (ms):
 // repeat 4.18 -> 3.40, zeros 3.88 -> 3.26, bmp 4.05 -> 3.48, mixed 6.67 -> 6.60; the bookkeeping
-// costs text 8.89 -> 9.14 and random 5.48 -> 5.71 (no runs there)
-#ifndef DMX_DF_SKIP
-#define DMX_DF_SKIP 1
-#endif
-constexpr bool DF_SKIP = DMX_DF_SKIP != 0;
-// level 2: a run that the continuation test verifies up to the segment end (a terminal run)
-// ends the match rounds: its candidates are stored by one vector-store loop and the match
-// bitmap of its positions is written as ones (see run_lo).  0: every remaining round stores
-// its candidates and the bitmap is built from them
-#ifndef DMX_DF_TERMRUN
-#define DMX_DF_TERMRUN 1
-#endif
-// level 2, with DMX_DF_RUNLEN: a segment with a terminal run also compares the round before the
-// run at the run's distance, so the parse knows from where on the data repeats (run_e); 0: from
-// the run's first round on
-#ifndef DMX_DF_RUNBACK
-#define DMX_DF_RUNBACK 1
-#endif
-// level 2, with DMX_DF_TERMRUN: the parse takes a match length from the proven run instead of
-// comparing bytes where both ends of the match lie inside it (see run_e and known_len)
-#ifndef DMX_DF_RUNLEN
-#define DMX_DF_RUNLEN 1
-#endif
-// level 2, segments with a terminal run: the parse walk's literal skip looks up to four bitmap
-// words ahead with the quad's four lanes (with DMX_DF_RUNLEN; see parse_walk)
-#ifndef DMX_DF_LITSKIP
-#define DMX_DF_LITSKIP 1
-#endif
+// costs text 8.89 -> 9.14 and random 5.48 -> 5.71 (no runs there).  In the 32 KiB kernel a run
+// that the test verifies up to the segment end (a terminal run) ends the match rounds: its
+// candidates are stored by one vector-store loop and the match bitmap of its positions is
+// written as ones (see run_lo).  Such a segment also compares the round before the run at the
+// run's distance, so the parse knows from where on the data repeats (run_e); its parse takes a
+// match length from the proven run instead of comparing bytes where both ends of the match lie
+// inside it (see known_len), and its literal skip looks up to four bitmap words ahead with the
+// quad's four lanes (see parse_walk).
+//
 // Early load (32 KiB segments): the next segment of the workgroup is loaded into the match
 // rounds' table, dead once the rounds end, while the parse walk runs; the table and the byte
 // image are two buffers that swap roles on every segment, and the barriers at a segment's end
-// wait for LDS only (see deflate_segments).  0: the next segment is loaded into the image itself
-// after the token words, and the loop's closing barrier waits for it.  2: the early load with
-// the image and the table at fixed addresses: the loaded bytes are copied from the table to the
-// image, LDS to LDS, at the segment's end (the hot loops keep their constant LDS addresses)
-#ifndef DMX_DF_EARLYLOAD
-#define DMX_DF_EARLYLOAD 1
-#endif
-// (32 KiB segments only: two workgroups of the 16 KiB kernel share a CU, so one's wait for memory
-// passes behind the other's work, and the kernel has no register to spare for a buffer base)
-constexpr int df_early(int seg) { return seg >= 32768 ? DMX_DF_EARLYLOAD : 0; }
-// the early load is issued by the workgroup's upper eight waves, which the parse walk leaves
-// idle (0: by all sixteen, two loads each)
-#ifndef DMX_DF_EARLYHALF
-#define DMX_DF_EARLYHALF 1
-#endif
-// the front kernel counts the symbols (the emission kernel skips its histogram pass)
-#ifndef DMX_DF_HIST
-#define DMX_DF_HIST 0
-#endif
-// (round 4's DMX_EM_PREF -- token words loaded two blocks ahead -- measured no gain, DESIGN
-// 4.1, and was removed in round 6 with the per-part token sources of 64 KiB blocks)
-// level 2: half-size parse chunks for segments without a run (see the parse walk)
-#ifndef DMX_DF_ADAPT
-#define DMX_DF_ADAPT 0
-#endif
-constexpr bool DF_EARLY_HALF = DMX_DF_EARLYHALF != 0 && !DMX_DF_ADAPT;  // (those chunks take every wave)
+// wait for LDS only (see deflate_segments).  The load is issued by the workgroup's upper eight
+// waves, which the parse walk leaves idle.  The 16 KiB kernel loads the next segment into the
+// image itself after the token words, and the loop's closing barrier waits for it: two of its
+// workgroups share a CU, so one's wait for memory passes behind the other's work, and the kernel
+// has no register to spare for a buffer base.
+constexpr bool df_early(int seg) { return seg >= 32768; }
 // token-word count of a segment without any match (k_deflate_emit then reads its input's bytes)
 constexpr uint32_t EM_ALL_LITERALS = 0xFFFFFFFFu;
 
@@ -469,9 +396,9 @@ __device__ __forceinline__ RunPlan plan_run(uint32_t v, uint32_t r) {
 // ---------------------------------------------------------------------------------------
 // the segment kernel: 1024 threads (16 waves) per segment, one workgroup per CU
 // ---------------------------------------------------------------------------------------
-// The byte image, the candidates and the match rounds' table.  SWAP (df_early 1): the image and
+// The byte image, the candidates and the match rounds' table.  EARLY (df_early): the image and
 // the table are two buffers of one array that swap roles on every segment (see deflate_segments).
-template <int SEG, bool SWAP>
+template <int SEG, bool EARLY>
 struct DfBufs;
 template <int SEG>
 struct DfBufs<SEG, false> {
@@ -488,21 +415,19 @@ struct DfBufs<SEG, true> {
     alignas(16) uint16_t cand[SEG + 8];
 };
 template <int SEG>
-struct DfSmem : DfBufs<SEG, df_early(SEG) == 1> {
-    static constexpr bool EARLY = df_early(SEG) != 0;  // the next segment loads during the parse walk
-    static constexpr bool SWAP = df_early(SEG) == 1;   // the image and the table swap roles
+struct DfSmem : DfBufs<SEG, df_early(SEG)> {
+    // the next segment loads during the parse walk, and the image and the table swap roles
+    static constexpr bool EARLY = df_early(SEG);
     static constexpr int NWALK = (SEG + DF_CHUNK - 1) / DF_CHUNK;
-    static constexpr int NWALK_MAX = DMX_DF_ADAPT ? (SEG + DF_CHUNK / 2 - 1) / (DF_CHUNK / 2) : NWALK;
     static constexpr int HB = df_hash_bits(SEG);
     static constexpr int HT = 1 << HB;  // entries per hash table
     static constexpr int UW = 2 * HT;
     uint32_t mmap[SEG / 32];    // "a verified match of >= 3 starts here" (match rounds)
     uint32_t tokmap[SEG / 32];  // token-start bitmap (parse walk; chunks share boundary words)
-    uint16_t lasttok[NWALK_MAX + 1];  // last token start of each parse chunk
+    uint16_t lasttok[NWALK + 1];  // last token start of each parse chunk
     uint32_t scan[4 * DF_NT / 64];
     uint32_t sh[64];  // 43: backward mismatch tag, 44: run candidate, 45 / 47: terminal run,
                       // 46: mismatch tag, 48..62: divisor-period tags
-    uint32_t hist[DMX_DF_HIST ? 320 : 1];  // the segment's symbol counts (see deflate_tok_stride)
 };
 static_assert(sizeof(DfSmem<32768>) <= 160 * 1024, "the front kernel's LDS fits a CU's 160 KiB");
 
@@ -583,10 +508,14 @@ __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t 
         const uint4* src = reinterpret_cast<const uint4*>(nsrc) + t;
         // one wave-instruction writes 64 x 16 B contiguously from a wave-uniform LDS base
         uint4* dst = reinterpret_cast<uint4*>(image) + (t & ~63);
-        if constexpr (df_early(SEG) != 0 && DF_EARLY_HALF) {
-            // (the asm form below) Waves 8..15 issue all of it, four loads each: the parse walk
-            // that follows occupies waves 0..7 only (NWALK quads), which then start at once
-            static_assert(4 * DfSmem<SEG>::NWALK_MAX <= DF_NT / 2, "the walk leaves the upper waves idle");
+        if constexpr (df_early(SEG)) {
+            // As an asm statement: the compiler counts a global_load_lds it knows of as a pending
+            // LDS write and waits vmcnt(0) before the wave's next LDS store or atomic -- the parse
+            // walk's first token bit.  The caller waits for these loads itself.  (M0, the LDS
+            // base of the load, is the compiler's: saved and restored in the same statement.)
+            // Waves 8..15 issue all of it, four loads each: the parse walk that follows occupies
+            // waves 0..7 only (NWALK quads), which then start at once
+            static_assert(4 * DfSmem<SEG>::NWALK <= DF_NT / 2, "the walk leaves the upper waves idle");
             if (t >= DF_NT / 2) {
                 const uint32_t base = __builtin_amdgcn_readfirstlane(
                     (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(dst - DF_NT / 2));
@@ -599,22 +528,6 @@ __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t 
                                  : "v"(src - DF_NT / 2 + k * (DF_NT / 2)), "s"(base + (uint32_t)(k * DF_NT * 8))
                                  : "memory");
                 }
-            }
-        } else if constexpr (df_early(SEG) != 0) {
-            // As an asm statement: the compiler counts a global_load_lds it knows of as a pending
-            // LDS write and waits vmcnt(0) before the wave's next LDS store or atomic -- the parse
-            // walk's first token bit.  The caller waits for these loads itself.  (M0, the LDS
-            // base of the load, is the compiler's: saved and restored in the same statement.)
-            const uint32_t base = __builtin_amdgcn_readfirstlane(
-                (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)dst);
-#pragma unroll
-            for (int k = 0; k < SEG / (16 * DF_NT); k++) {
-                uint32_t keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                             "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep)
-                             : "v"(src + k * DF_NT), "s"(base + (uint32_t)(k * DF_NT * 16))
-                             : "memory");
             }
         } else {
 #pragma unroll
@@ -667,10 +580,10 @@ __device__ __forceinline__ void df_load_at(uint8_t* dbytes, uint32_t off, const 
 template <int SEG, bool L3, bool BATCH, bool DICT>
 __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG>& S, uint64_t seg,
                                                 uint32_t& staged, [[maybe_unused]] uint32_t iw) {
-    constexpr bool EARLY = DfSmem<SEG>::EARLY, SWAP = DfSmem<SEG>::SWAP;
-    // the byte image and the match rounds' table (SWAP: the buffer at word iw and the other one)
+    constexpr bool EARLY = DfSmem<SEG>::EARLY;
+    // the byte image and the match rounds' table (EARLY: the buffer at word iw and the other one)
     uint32_t *data32, *U;
-    if constexpr (SWAP) {
+    if constexpr (EARLY) {
         data32 = &S.buf[0][0] + iw;
         U = &S.buf[0][0] + ((uint32_t)DfSmem<SEG>::BW - iw);
     } else {
@@ -688,10 +601,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
     uint8_t* const dbytes = reinterpret_cast<uint8_t*>(data32);
     // (32 KiB segments only: the 16 KiB kernel sits at its 64-register limit, and with this code
     // in it the compiler spills its kernel arguments to scratch)
-    constexpr bool TERMRUN = DF_SKIP && !L3 && SEG >= 32768 && DMX_DF_TERMRUN;
+    constexpr bool TERMRUN = !L3 && SEG >= 32768;
     constexpr uint32_t RUN_NONE = 0xFFFFFFFFu;
-    constexpr bool RUNLEN = TERMRUN && DMX_DF_RUNLEN;
-    constexpr bool RUNBACK = RUNLEN && DMX_DF_RUNBACK;
     DMX_PHASE(A.dbg, seg, 0);
 
     // ---- load the segment into LDS (16 B per lane when aligned) ------------------------
@@ -715,10 +626,9 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         if (t < NMAP) S.tokmap[t] = 0;
         if (t == 0) S.sh[46] = 0;  // the match rounds' mismatch tag (run continuation)
         if (TERMRUN && t == 1) S.sh[45] = RUN_NONE;  // its terminal run's first position
-        if (RUNBACK && t == 2) S.sh[43] = 0;  // the run's last mismatch in the round before it
+        if (TERMRUN && t == 2) S.sh[43] = 0;  // the run's last mismatch in the round before it
         if (t >= 48 && t < 63) S.sh[t] = 0;  // its divisor-period tags
-        if (DMX_DF_HIST && t < 320) S.hist[t] = 0;
-        if (level >= 2 && EARLY) {  // (SWAP: the previous segment's image, dead since its last barrier)
+        if (level >= 2 && EARLY) {  // (the previous segment's image, dead since its last barrier)
             uint4* const u4 = reinterpret_cast<uint4*>(U);
             for (int i = t; i < 2 * HT / 4; i += DF_NT) u4[i] = make_uint4(0, 0, 0, 0);
         } else if (level >= 2)
@@ -730,7 +640,6 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
     staged = 0;
 
     if (level != 0) {
-        bool any_skip = false;  // (uniform) the run continuation took a round of this segment
         // Terminal run (uniform): the positions [run_lo, nb) repeat at distance run_d up to the
         // segment end, so every one of them with four bytes left has the candidate run_d.  The
         // match rounds end at run_lo (a round's first position).  The round that finds the run
@@ -763,267 +672,213 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             constexpr uint32_t HB = DfSmem<SEG>::HB;
             const uint2* const tab = reinterpret_cast<const uint2*>(U);
             uint32_t* const cand32 = reinterpret_cast<uint32_t*>(S.cand);
-            uint32_t ph0 = 0, ph1 = 0, pp0 = 0, pf0 = 0, pf1 = 0;  // previous round: hashes, p0, fp16s
-            bool pok0 = false, pok1 = false;
             constexpr uint32_t NOH = 0xFFFFFFFFu;  // "no hash" for the neighbour compares
-            if (level == 3 && DF_L3_LINK_ROUNDS) {
-                // Level 3 builds links for the chain search below: rounds of DF_L3_ROUND
-                // positions, each position linked to the latest occurrence of its key before
-                // its round (or to its pair partner, in-thread), so consecutive links skip at
-                // most one round -- the hash chain of the reference's getMatchesSlow scan
-                // (deflate.hpp:268-304) in a form the parallel rounds can build.
-                const bool act = t < DF_L3_ROUND / 2;
-                for (uint32_t r0 = 0; r0 < nb; r0 += DF_L3_ROUND) {
-                    const uint32_t p0 = r0 + 2 * t, p1 = p0 + 1;
-                    uint32_t h0 = NOH, h1 = NOH, fa0 = 0, fa1 = 0, k0 = 0, k1 = 1;
-                    bool ok0 = false, ok1 = false;
-                    if (act) {
-                        const uint32_t wa = data32[p0 >> 2], wb = data32[(p0 >> 2) + 1];
-                        k0 = __builtin_amdgcn_alignbyte(wb, wa, p0 & 3);
-                        k1 = __builtin_amdgcn_alignbyte(wb, wa, (p0 & 3) + 1);
-                        const uint32_t prod0 = k0 * 0x1E35A7BDu, prod1 = k1 * 0x1E35A7BDu;
-                        ok0 = p0 + 4 <= nb;
-                        ok1 = p1 + 4 <= nb;
-                        h0 = ok0 ? prod0 >> (32 - HB) : NOH;
-                        h1 = ok1 ? prod1 >> (32 - HB) : NOH;
-                        fa0 = (prod0 >> (32 - HB - 16)) & 0xFFFFu;
-                        fa1 = (prod1 >> (32 - HB - 16)) & 0xFFFFu;
-                        const uint32_t hn = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)(pok0 ? ph0 : NOH), 0x101, 0xF, 0xF, false);
-                        if (pok0 && ph0 != (pok1 ? ph1 : NOH)) atomicMax(&U[2 * ph0], ((pp0 + 1) << 16) | pf0);
-                        if (pok1 && ph1 != hn) atomicMax(&U[2 * ph1], ((pp0 + 2) << 16) | pf1);
+            // One round; cur receives this round's hashes for the next round's latest-occurrence
+            // updates, prev holds the previous round's.  Rounds go in pairs with the two states
+            // swapping roles (no register copies), and rounds that lie wholly inside the
+            // segment skip the bounds tests (`full`, a constant in each call).  Rounds of RP
+            // positions: 2 * DF_NT at level 2; level 3 may use shorter rounds (DF_L3_RP, the
+            // first RP / 2 threads active) so the first-in-round links skip fewer occurrences
+            // for its chain search, with a wider round number and a narrower fingerprint.
+            struct RoundState {
+                uint32_t h0, h1, p0, f0, f1;
+                bool ok0, ok1;
+            };
+            bool skipped = false;  // a round skipped by the run continuation (uniform)
+            auto run_rounds = [&](auto rpc) {
+                constexpr uint32_t RP = decltype(rpc)::value;
+                constexpr uint32_t NR = SEG / RP;
+                constexpr uint32_t TAGB = NR <= 16 ? 4 : NR <= 32 ? 5 : NR <= 64 ? 6 : 7;
+                static_assert(NR <= 128, "round number is at most 7 bits");
+                constexpr uint32_t FPB = 17 - TAGB;  // fingerprint bits in the first entry
+                const bool act = RP >= 2 * DF_NT || t < (int)(RP / 2);
+                const uint32_t tt = RP >= 2 * DF_NT ? (uint32_t)t : (uint32_t)t & (RP / 2 - 1);
+                // Run continuation (level 2): after a round in which at least 120 of the last
+                // 128 positions found a candidate, the next round tests the rest of the segment at one
+                // distance d (the candidate of that round's last position): the words at q and
+                // q - d, neighbouring lanes on neighbouring words (no bank conflicts), the first
+                // mismatch by an LDS atomic.  Every round
+                // whose positions all lie before it (their 4-byte keys verified at d) takes d
+                // as every candidate and skips the hash table: no atomics, no lookup, no
+                // barrier (its positions are never entered, so later rounds see older,
+                // farther occurrences of those keys: still verified candidates).  Long runs of
+                // one period (zeros, a repeated record, an image row) cost one compare per
+                // byte instead of two atomics and a lookup per position -- the parallel form of
+                // zlib not inserting the positions inside a long match (deflate_fast's
+                // max_insert_length).  A run that ends inside the tested round waits 1, 2, 4
+                // .. 16 normal rounds before the next test.  LDS: sh[44] = that candidate (0:
+                // no test), written by the round's last thread; sh[46] = (round + 1) << 16 |
+                // 0xFFFF - first mismatch (atomicMax: no reset between rounds).
+                constexpr bool SKIP = RP == 2 * DF_NT;
+                uint32_t skip_d = 0, skip_end = 0, wait = 0, backoff = 1;  // uniform
+                skipped = false;
+                bool pend = false;  // the previous round was a normal one (sh[44] is read)
+                auto round = [&](uint32_t r0, uint32_t rr, RoundState& cur, const RoundState& prev, auto full) {
+                    constexpr bool FULL = decltype(full)::value;
+                    const uint32_t p0 = r0 + 2 * tt, p1 = p0 + 1;
+                    if (SKIP && skip_d) {
+                        if (r0 + RP <= skip_end || (!TERMRUN && skip_end >= nb)) {  // inside the verified run
+                            if (FULL || p0 < nb)
+                                cand32[p0 >> 1] = (FULL || p0 + 4 <= nb ? skip_d : 0u) |
+                                                  ((FULL || p1 + 4 <= nb ? skip_d : 0u) << 16);
+                            cur = RoundState{NOH, NOH, p0, 0, 0, false, false};
+                            skipped = true;
+                            return;
+                        }
+                        skip_d = 0;
+                    }
+                    uint32_t dlr = 0;  // (issued first: its latency overlaps the data words')
+                    if (SKIP && pend) dlr = S.sh[44];
+                    const uint32_t i0 = p0 >> 2, sh = p0 & 3;  // sh = 0 or 2
+                    const uint32_t wa = data32[i0], wb = data32[i0 + 1];
+                    const uint32_t k0 = __builtin_amdgcn_alignbyte(wb, wa, sh);
+                    const uint32_t k1 = __builtin_amdgcn_alignbyte(wb, wa, sh + 1);
+                    const uint32_t prod0 = k0 * 0x1E35A7BDu;
+                    const uint32_t prod1 = k1 * 0x1E35A7BDu;
+                    const bool ok0 = act && (FULL || p0 + 4 <= nb), ok1 = act && (FULL || p1 + 4 <= nb);
+                    const uint32_t h0 = ok0 ? prod0 >> (32 - HB) : NOH, h1 = ok1 ? prod1 >> (32 - HB) : NOH;
+                    const uint32_t fa0 = (prod0 >> (32 - HB - 16)) & 0xFFFFu, fa1 = (prod1 >> (32 - HB - 16)) & 0xFFFFu;
+                    // first occurrence in this round: p1 needs no update when p0 has its hash, p0
+                    // none when p0 - 1 (the previous lane's p1, by DPP within rows of 16) has it
+                    // (issued before the head updates, which do not wait for the data words: the
+                    // wait for the words then finds no atomic in flight)
+                    const uint32_t hl = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)h1, 0x111, 0xF, 0xF, false);
+                    const uint32_t rtag = rr << (32 - TAGB);
+                    if (ok0 && h0 != hl)
+                        atomicMax(&U[2 * h0 + 1], rtag | ((0x7FFFu - p0) << FPB) | (fa0 >> (16 - FPB)));
+                    if (ok1 && h1 != h0)
+                        atomicMax(&U[2 * h1 + 1], rtag | ((0x7FFFu - p1) << FPB) | (fa1 >> (16 - FPB)));
+                    // latest occurrence, for the previous round's positions: its p0 needs no update
+                    // when its p0 + 1 has the hash, p0 + 1 none when p0 + 2 (the next lane's) has it
+                    const uint32_t hn = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)(prev.ok0 ? prev.h0 : NOH), 0x101, 0xF, 0xF, false);
+                    if (prev.ok0 && prev.h0 != (prev.ok1 ? prev.h1 : NOH))
+                        atomicMax(&U[2 * prev.h0], ((prev.p0 + 1) << 16) | prev.f0);
+                    if (prev.ok1 && prev.h1 != hn) atomicMax(&U[2 * prev.h1], ((prev.p0 + 2) << 16) | prev.f1);
+                    bool tested = false;
+                    if (SKIP && pend) {
+                        pend = false;
+                        uint32_t dl = __builtin_amdgcn_readfirstlane(dlr);
+                        wait -= wait ? 1u : 0u;
+                        if (!wait && dl) {
+                            tested = true;
+                            // Periodic data: the trigger's candidate is a first occurrence in an
+                            // earlier round, often a multiple of the period.  The largest k <= 16
+                            // (dl % k == 0) whose dl / k repeats the 256 bytes at r0 gives the
+                            // tested distance (64 threads per k, one word each; a mismatch tags
+                            // sh[48 + k - 2] with the round); the test below then verifies it.
+                            {
+                                const uint32_t ki = (uint32_t)t >> 6, k = ki + 2, bq = r0 + 4 * ((uint32_t)t & 63);
+                                if (ki < 15 && dl % k == 0 && bq + 4 <= nb) {
+                                    const uint32_t dk = dl / k, ia = (bq - dk) >> 2, sk = (bq - dk) & 3;
+                                    if (data32[bq >> 2] != __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sk))
+                                        atomicMax(&S.sh[48 + ki], rr + 1);
+                                }
+                            }
+                            __syncthreads();  // (uniform: dl and wait are the same in every wave)
+                            uint32_t dsel = dl;
+#pragma unroll
+                            for (uint32_t k = 2; k <= 16; k++)
+                                dsel = (dl % k == 0 && S.sh[48 + k - 2] != rr + 1) ? dl / k : dsel;
+                            dl = __builtin_amdgcn_readfirstlane(dsel);
+                            // words r0 / 4 + t + 1024 j (neighbouring lanes, neighbouring words:
+                            // no bank conflicts) against the words dl bytes before them
+                            skip_d = dl;
+                            const uint32_t sa = (r0 - dl) & 3;  // (r0 is a multiple of 4)
+                            uint32_t mm = 0xFFFFFFFFu;
+#pragma unroll
+                            for (int j = 7; j >= 0; j--) {
+                                const uint32_t bq = r0 + 4 * ((uint32_t)t + DF_NT * j);
+                                if (bq < nb) {
+                                    const uint32_t ia = (bq - dl) >> 2;
+                                    const uint32_t df = data32[bq >> 2] ^
+                                                        __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sa);
+                                    mm = df ? bq + ((uint32_t)__builtin_ctz(df) >> 3) : mm;
+                                }
+                            }
+                            if (mm != 0xFFFFFFFFu) atomicMax(&S.sh[46], ((rr + 1) << 16) | (0xFFFFu - mm));
+                        }
                     }
                     __syncthreads();
-                    if (act) {
-                        const uint32_t e0 = tab[ok0 ? h0 : 0u].x, e1 = tab[ok1 ? h1 : 0u].x;
-                        const uint32_t c0 = ok0 && e0 && (e0 & 0xFFFFu) == fa0 ? p0 + 1u - (e0 >> 16) : 0u;
-                        uint32_t c1 = ok1 && e1 && (e1 & 0xFFFFu) == fa1 ? p1 + 1u - (e1 >> 16) : 0u;
-                        if (ok1 && ok0 && k1 == k0) c1 = 1;
-                        cand32[p0 >> 1] = c0 | (c1 << 16);
+                    if (SKIP && tested) {
+                        // positions p < m - 3 have their key verified at skip_d (m: first mismatch)
+                        const uint32_t mt = __builtin_amdgcn_readfirstlane(S.sh[46]);
+                        const uint32_t m = (mt >> 16) == rr + 1 ? 0xFFFFu - (mt & 0xFFFFu) : 0xFFFFFFFFu;
+                        skip_end = m >= nb ? nb : (m >= 3 ? m - 3 : 0u);
+                        if (TERMRUN && skip_end >= nb) {  // a terminal run: the rounds end here
+                            if (t == 0) {                  // (see run_lo)
+                                S.sh[45] = r0;
+                                S.sh[47] = skip_d;
+                            }
+                            skipped = true;
+                            return;
+                        }
+                        if (r0 + RP <= skip_end || (!TERMRUN && skip_end >= nb)) {  // this round is inside the run
+                            if (act && (FULL || p0 < nb))
+                                cand32[p0 >> 1] = (ok0 ? skip_d : 0u) | ((ok1 ? skip_d : 0u) << 16);
+                            cur = RoundState{NOH, NOH, p0, 0, 0, false, false};
+                            backoff = 1;
+                            skipped = true;
+                            return;
+                        }
+                        skip_d = 0;
+                        wait = backoff;
+                        backoff = min(2 * backoff, 16u);
                     }
-                    ph0 = h0;
-                    ph1 = h1;
-                    pp0 = p0;
-                    pf0 = fa0;
-                    pf1 = fa1;
-                    pok0 = ok0;
-                    pok1 = ok1;
-                    __syncthreads();
-                }
-            } else {
-                // One round; cur receives this round's hashes for the next round's latest-occurrence
-                // updates, prev holds the previous round's.  Rounds go in pairs with the two states
-                // swapping roles (no register copies), and rounds that lie wholly inside the
-                // segment skip the bounds tests (`full`, a constant in each call).  Rounds of RP
-                // positions: 2 * DF_NT at level 2; level 3 may use shorter rounds (DF_L3_RP, the
-                // first RP / 2 threads active) so the first-in-round links skip fewer occurrences
-                // for its chain search, with a wider round number and a narrower fingerprint.
-                struct RoundState {
-                    uint32_t h0, h1, p0, f0, f1;
-                    bool ok0, ok1;
-                };
-                bool skipped = false;  // a round skipped by the run continuation (uniform)
-                auto run_rounds = [&](auto rpc) {
-                    constexpr uint32_t RP = decltype(rpc)::value;
-                    constexpr uint32_t NR = SEG / RP;
-                    constexpr uint32_t TAGB = NR <= 16 ? 4 : NR <= 32 ? 5 : NR <= 64 ? 6 : 7;
-                    static_assert(NR <= 128, "round number is at most 7 bits");
-                    constexpr uint32_t FPB = 17 - TAGB;  // fingerprint bits in the first entry
-                    const bool act = RP >= 2 * DF_NT || t < (int)(RP / 2);
-                    const uint32_t tt = RP >= 2 * DF_NT ? (uint32_t)t : (uint32_t)t & (RP / 2 - 1);
-                    // Run continuation (level 2): after a round in which at least 120 of the last
-                    // 128 positions found a candidate, the next round tests the rest of the segment at one
-                    // distance d (the candidate of that round's last position): the words at q and
-                    // q - d, neighbouring lanes on neighbouring words (no bank conflicts), the first
-                    // mismatch by an LDS atomic.  Every round
-                    // whose positions all lie before it (their 4-byte keys verified at d) takes d
-                    // as every candidate and skips the hash table: no atomics, no lookup, no
-                    // barrier (its positions are never entered, so later rounds see older,
-                    // farther occurrences of those keys: still verified candidates).  Long runs of
-                    // one period (zeros, a repeated record, an image row) cost one compare per
-                    // byte instead of two atomics and a lookup per position -- the parallel form of
-                    // zlib not inserting the positions inside a long match (deflate_fast's
-                    // max_insert_length).  A run that ends inside the tested round waits 1, 2, 4
-                    // .. 16 normal rounds before the next test.  LDS: sh[44] = that candidate (0:
-                    // no test), written by the round's last thread; sh[46] = (round + 1) << 16 |
-                    // 0xFFFF - first mismatch (atomicMax: no reset between rounds).
-                    constexpr bool SKIP = DF_SKIP && RP == 2 * DF_NT;
-                    uint32_t skip_d = 0, skip_end = 0, wait = 0, backoff = 1;  // uniform
-                    skipped = false;
-                    bool pend = false;  // the previous round was a normal one (sh[44] is read)
-                    auto round = [&](uint32_t r0, uint32_t rr, RoundState& cur, const RoundState& prev, auto full) {
-                        constexpr bool FULL = decltype(full)::value;
-                        const uint32_t p0 = r0 + 2 * tt, p1 = p0 + 1;
-                        if (SKIP && skip_d) {
-                            if (r0 + RP <= skip_end || (!TERMRUN && skip_end >= nb)) {  // inside the verified run
-                                if (FULL || p0 < nb)
-                                    cand32[p0 >> 1] = (FULL || p0 + 4 <= nb ? skip_d : 0u) |
-                                                      ((FULL || p1 + 4 <= nb ? skip_d : 0u) << 16);
-                                cur = RoundState{NOH, NOH, p0, 0, 0, false, false};
-                                skipped = true;
-                                return;
-                            }
-                            skip_d = 0;
-                        }
-                        uint32_t dlr = 0;  // (issued first: its latency overlaps the data words')
-                        if (SKIP && pend) dlr = S.sh[44];
-                        const uint32_t i0 = p0 >> 2, sh = p0 & 3;  // sh = 0 or 2
-                        const uint32_t wa = data32[i0], wb = data32[i0 + 1];
-                        const uint32_t k0 = __builtin_amdgcn_alignbyte(wb, wa, sh);
-                        const uint32_t k1 = __builtin_amdgcn_alignbyte(wb, wa, sh + 1);
-                        const uint32_t prod0 = k0 * 0x1E35A7BDu;
-                        const uint32_t prod1 = k1 * 0x1E35A7BDu;
-                        const bool ok0 = act && (FULL || p0 + 4 <= nb), ok1 = act && (FULL || p1 + 4 <= nb);
-                        const uint32_t h0 = ok0 ? prod0 >> (32 - HB) : NOH, h1 = ok1 ? prod1 >> (32 - HB) : NOH;
-                        const uint32_t fa0 = (prod0 >> (32 - HB - 16)) & 0xFFFFu, fa1 = (prod1 >> (32 - HB - 16)) & 0xFFFFu;
-                        // first occurrence in this round: p1 needs no update when p0 has its hash, p0
-                        // none when p0 - 1 (the previous lane's p1, by DPP within rows of 16) has it
-                        // (issued before the head updates, which do not wait for the data words: the
-                        // wait for the words then finds no atomic in flight)
-                        const uint32_t hl = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)h1, 0x111, 0xF, 0xF, false);
-                        const uint32_t rtag = rr << (32 - TAGB);
-                        if (ok0 && h0 != hl)
-                            atomicMax(&U[2 * h0 + 1], rtag | ((0x7FFFu - p0) << FPB) | (fa0 >> (16 - FPB)));
-                        if (ok1 && h1 != h0)
-                            atomicMax(&U[2 * h1 + 1], rtag | ((0x7FFFu - p1) << FPB) | (fa1 >> (16 - FPB)));
-                        // latest occurrence, for the previous round's positions: its p0 needs no update
-                        // when its p0 + 1 has the hash, p0 + 1 none when p0 + 2 (the next lane's) has it
-                        const uint32_t hn = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)(prev.ok0 ? prev.h0 : NOH), 0x101, 0xF, 0xF, false);
-                        if (prev.ok0 && prev.h0 != (prev.ok1 ? prev.h1 : NOH))
-                            atomicMax(&U[2 * prev.h0], ((prev.p0 + 1) << 16) | prev.f0);
-                        if (prev.ok1 && prev.h1 != hn) atomicMax(&U[2 * prev.h1], ((prev.p0 + 2) << 16) | prev.f1);
-                        bool tested = false;
-                        if (SKIP && pend) {
-                            pend = false;
-                            uint32_t dl = __builtin_amdgcn_readfirstlane(dlr);
-                            wait -= wait ? 1u : 0u;
-#ifdef DMX_DF_SKIPDBG
-                            if (seg == 10 && t == 0) printf("seg %u round %u dl %u wait %u\n", (unsigned)seg, rr, dl, wait);
-#endif
-                            if (!wait && dl) {
-                                tested = true;
-                                // Periodic data: the trigger's candidate is a first occurrence in an
-                                // earlier round, often a multiple of the period.  The largest k <= 16
-                                // (dl % k == 0) whose dl / k repeats the 256 bytes at r0 gives the
-                                // tested distance (64 threads per k, one word each; a mismatch tags
-                                // sh[48 + k - 2] with the round); the test below then verifies it.
-                                {
-                                    const uint32_t ki = (uint32_t)t >> 6, k = ki + 2, bq = r0 + 4 * ((uint32_t)t & 63);
-                                    if (ki < 15 && dl % k == 0 && bq + 4 <= nb) {
-                                        const uint32_t dk = dl / k, ia = (bq - dk) >> 2, sk = (bq - dk) & 3;
-                                        if (data32[bq >> 2] != __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sk))
-                                            atomicMax(&S.sh[48 + ki], rr + 1);
-                                    }
-                                }
-                                __syncthreads();  // (uniform: dl and wait are the same in every wave)
-                                uint32_t dsel = dl;
-#pragma unroll
-                                for (uint32_t k = 2; k <= 16; k++)
-                                    dsel = (dl % k == 0 && S.sh[48 + k - 2] != rr + 1) ? dl / k : dsel;
-                                dl = __builtin_amdgcn_readfirstlane(dsel);
-                                // words r0 / 4 + t + 1024 j (neighbouring lanes, neighbouring words:
-                                // no bank conflicts) against the words dl bytes before them
-                                skip_d = dl;
-                                const uint32_t sa = (r0 - dl) & 3;  // (r0 is a multiple of 4)
-                                uint32_t mm = 0xFFFFFFFFu;
-#pragma unroll
-                                for (int j = 7; j >= 0; j--) {
-                                    const uint32_t bq = r0 + 4 * ((uint32_t)t + DF_NT * j);
-                                    if (bq < nb) {
-                                        const uint32_t ia = (bq - dl) >> 2;
-                                        const uint32_t df = data32[bq >> 2] ^
-                                                            __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sa);
-                                        mm = df ? bq + ((uint32_t)__builtin_ctz(df) >> 3) : mm;
-                                    }
-                                }
-                                if (mm != 0xFFFFFFFFu) atomicMax(&S.sh[46], ((rr + 1) << 16) | (0xFFFFu - mm));
-                            }
-                        }
-                        __syncthreads();
-                        if (SKIP && tested) {
-                            // positions p < m - 3 have their key verified at skip_d (m: first mismatch)
-                            const uint32_t mt = __builtin_amdgcn_readfirstlane(S.sh[46]);
-                            const uint32_t m = (mt >> 16) == rr + 1 ? 0xFFFFu - (mt & 0xFFFFu) : 0xFFFFFFFFu;
-                            skip_end = m >= nb ? nb : (m >= 3 ? m - 3 : 0u);
-#ifdef DMX_DF_SKIPDBG
-                            if (seg == 10 && t == 0) printf("seg %u round %u tested m %u skip_end %u\n", (unsigned)seg, rr, m, skip_end);
-#endif
-                            if (TERMRUN && skip_end >= nb) {  // a terminal run: the rounds end here
-                                if (t == 0) {                  // (see run_lo)
-                                    S.sh[45] = r0;
-                                    S.sh[47] = skip_d;
-                                }
-                                skipped = true;
-                                return;
-                            }
-                            if (r0 + RP <= skip_end || (!TERMRUN && skip_end >= nb)) {  // this round is inside the run
-                                if (act && (FULL || p0 < nb))
-                                    cand32[p0 >> 1] = (ok0 ? skip_d : 0u) | ((ok1 ? skip_d : 0u) << 16);
-                                cur = RoundState{NOH, NOH, p0, 0, 0, false, false};
-                                backoff = 1;
-                                skipped = true;
-                                return;
-                            }
-                            skip_d = 0;
-                            wait = backoff;
-                            backoff = min(2 * backoff, 16u);
-                        }
-                        uint2 e0 = tab[ok0 ? h0 : 0u], e1 = tab[ok1 ? h1 : 0u];
-                        // both halves now: otherwise the compiler sinks the head half of e0 into the
-                        // not-first-in-round branch, a second LDS round trip after the first
-                        asm volatile("" : "+v"(e0.x), "+v"(e0.y), "+v"(e1.x), "+v"(e1.y));
-                        auto pick = [&](uint2 e, uint32_t p, uint32_t fa, bool ok) -> uint32_t {
-                            const uint32_t f = e.y, hd = e.x;
-                            const uint32_t q = 0x7FFFu - ((f >> FPB) & 0x7FFFu);
-                            const bool fr = ((f >> (32 - TAGB)) == rr) & (q < p) &
-                                            ((f & ((1u << FPB) - 1)) == (fa >> (16 - FPB)));
-                            const bool lt = (hd != 0u) & ((hd & 0xFFFFu) == fa);
-                            const uint32_t c = fr ? p - q : (lt ? p + 1u - (hd >> 16) : 0u);
-                            return ok ? c : 0u;
-                        };
-                        const uint32_t c0 = pick(e0, p0, fa0, ok0), c1 = pick(e1, p1, fa1, ok1);
-                        if (act && (FULL || p0 < nb)) cand32[p0 >> 1] = c0 | (c1 << 16);
-                        cur = RoundState{h0, h1, p0, fa0, fa1, ok0, ok1};
-                        if (SKIP) {  // the last wave: (nearly) all its positions have a candidate?
-                            if (t >= DF_NT - 64) {
-                                // (>= 120 of its 128: collided hash buckets leave a few without)
-                                const uint32_t nc = (uint32_t)__popcll(__ballot(c0 != 0u)) + (uint32_t)__popcll(__ballot(c1 != 0u));
-                                if (t == DF_NT - 1) S.sh[44] = nc >= 120 ? c1 : 0u;
-                            }
-                            pend = FULL;
-                        }
-                        __syncthreads();
+                    uint2 e0 = tab[ok0 ? h0 : 0u], e1 = tab[ok1 ? h1 : 0u];
+                    // both halves now: otherwise the compiler sinks the head half of e0 into the
+                    // not-first-in-round branch, a second LDS round trip after the first
+                    asm volatile("" : "+v"(e0.x), "+v"(e0.y), "+v"(e1.x), "+v"(e1.y));
+                    auto pick = [&](uint2 e, uint32_t p, uint32_t fa, bool ok) -> uint32_t {
+                        const uint32_t f = e.y, hd = e.x;
+                        const uint32_t q = 0x7FFFu - ((f >> FPB) & 0x7FFFu);
+                        const bool fr = ((f >> (32 - TAGB)) == rr) & (q < p) &
+                                        ((f & ((1u << FPB) - 1)) == (fa >> (16 - FPB)));
+                        const bool lt = (hd != 0u) & ((hd & 0xFFFFu) == fa);
+                        const uint32_t c = fr ? p - q : (lt ? p + 1u - (hd >> 16) : 0u);
+                        return ok ? c : 0u;
                     };
-                    using Full = std::integral_constant<bool, true>;
-                    using Part = std::integral_constant<bool, false>;
-                    const DeflateArgs& Ar = A;  // (shadowed by the round states below)
-                    RoundState A = {0, 0, 0, 0, 0, false, false}, B = A;
-                    uint32_t r0 = 0, rr = 0;
-                    // (a terminal run ends the rounds: skip_end >= nb only then)
-                    auto more = [&]() { return !(TERMRUN && SKIP) || skip_end < nb; };
-                    for (; r0 + 2 * RP + 3 <= nb && more(); r0 += 2 * RP, rr += 2) {  // two full rounds
-                        round(r0, rr, A, B, Full{});
-                        if (rr == 0) DMX_PHASE(Ar.dbg, seg, 12);
-                        if (!more()) break;
-                        round(r0 + RP, rr + 1, B, A, Full{});
-                        if (rr == 0) DMX_PHASE(Ar.dbg, seg, 13);
+                    const uint32_t c0 = pick(e0, p0, fa0, ok0), c1 = pick(e1, p1, fa1, ok1);
+                    if (act && (FULL || p0 < nb)) cand32[p0 >> 1] = c0 | (c1 << 16);
+                    cur = RoundState{h0, h1, p0, fa0, fa1, ok0, ok1};
+                    if (SKIP) {  // the last wave: (nearly) all its positions have a candidate?
+                        if (t >= DF_NT - 64) {
+                            // (>= 120 of its 128: collided hash buckets leave a few without)
+                            const uint32_t nc = (uint32_t)__popcll(__ballot(c0 != 0u)) + (uint32_t)__popcll(__ballot(c1 != 0u));
+                            if (t == DF_NT - 1) S.sh[44] = nc >= 120 ? c1 : 0u;
+                        }
+                        pend = FULL;
                     }
-                    for (; r0 < nb && more(); r0 += RP, rr++) {  // the rest (the last may be partial)
-                        round(r0, rr, A, B, Part{});
-                        const RoundState x = A;
-                        A = B;
-                        B = x;
-                    }
+                    __syncthreads();
                 };
-                if (level == 3 && DF_L3_RP != 2 * DF_NT)
-                    run_rounds(std::integral_constant<uint32_t, DF_L3_RP>{});
-                else
-                    run_rounds(std::integral_constant<uint32_t, 2 * DF_NT>{});
-                if (DF_SKIP && skipped) __syncthreads();  // skipped rounds end without a barrier
-                any_skip = skipped;
-                if (TERMRUN && skipped) {
-                    run_lo = __builtin_amdgcn_readfirstlane(S.sh[45]);
-                    run_d = __builtin_amdgcn_readfirstlane(S.sh[47]);
+                using Full = std::integral_constant<bool, true>;
+                using Part = std::integral_constant<bool, false>;
+                const DeflateArgs& Ar = A;  // (shadowed by the round states below)
+                RoundState A = {0, 0, 0, 0, 0, false, false}, B = A;
+                uint32_t r0 = 0, rr = 0;
+                // (a terminal run ends the rounds: skip_end >= nb only then)
+                auto more = [&]() { return !(TERMRUN && SKIP) || skip_end < nb; };
+                for (; r0 + 2 * RP + 3 <= nb && more(); r0 += 2 * RP, rr += 2) {  // two full rounds
+                    round(r0, rr, A, B, Full{});
+                    if (rr == 0) DMX_PHASE(Ar.dbg, seg, 12);
+                    if (!more()) break;
+                    round(r0 + RP, rr + 1, B, A, Full{});
+                    if (rr == 0) DMX_PHASE(Ar.dbg, seg, 13);
                 }
+                for (; r0 < nb && more(); r0 += RP, rr++) {  // the rest (the last may be partial)
+                    round(r0, rr, A, B, Part{});
+                    const RoundState x = A;
+                    A = B;
+                    B = x;
+                }
+            };
+            if (level == 3 && DF_L3_RP != 2 * DF_NT)
+                run_rounds(std::integral_constant<uint32_t, DF_L3_RP>{});
+            else
+                run_rounds(std::integral_constant<uint32_t, 2 * DF_NT>{});
+            if (skipped) __syncthreads();  // skipped rounds end without a barrier
+            if (TERMRUN && skipped) {
+                run_lo = __builtin_amdgcn_readfirstlane(S.sh[45]);
+                run_d = __builtin_amdgcn_readfirstlane(S.sh[47]);
             }
             DMX_PHASE(A.dbg, seg, 14);
         }
@@ -1054,31 +909,25 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     // and the parse measures the chosen one in full).  Then a link can only be
                     // longer if the 4 bytes ending at offset bl match as well (zlib's scan_end
                     // test, widened): one word compare per link, the full length only for the
-                    // links that pass.
-                    auto ml = [&](uint32_t a, uint32_t b, uint32_t m) {
-                        return DF_L3_U >= 2 ? matchlen_u(data32, a, b, m) : matchlen(data32, a, b, m);
-                    };
-                    auto rd = [&](uint32_t a) {
-                        return DF_L3_U >= 1 ? lds_rd32u(data32, a) : ld32u(data32, a);
-                    };
+                    // links that pass.  The tail test is one unaligned 4-byte LDS read and the
+                    // links' lengths come from unaligned 8-byte reads (matchlen_u).
                     uint32_t q = p - d0;
                     // (the first link with aligned words: neighbouring lanes read neighbouring
                     // bytes here, which unaligned 8-byte reads serve slower -- repeat +46 %)
-                    uint32_t bl = DF_L3_U >= 3 ? matchlen(data32, p, q, min(maxl, DF_L3_LONG))
-                                               : ml(p, q, min(maxl, DF_L3_LONG));
+                    uint32_t bl = matchlen(data32, p, q, min(maxl, DF_L3_LONG));
                     if (bl >= 3) bd = d0;
                     else bl = 2;  // (a fingerprint collision: no match yet)
-                    uint32_t tail = bl >= 3 ? rd(p + bl - 3) : 0u;
+                    uint32_t tail = bl >= 3 ? lds_rd32u(data32, p + bl - 3) : 0u;
                     for (int hop = 1; hop < DF_L3_DEPTH && bl < maxl && bl < DF_L3_LONG; hop++) {
                         const uint32_t dq = S.cand[q];
                         if (!dq) break;
                         q -= dq;
-                        if (bl >= 3 && rd(q + bl - 3) != tail) continue;
-                        const uint32_t L = ml(p, q, maxl);
+                        if (bl >= 3 && lds_rd32u(data32, q + bl - 3) != tail) continue;
+                        const uint32_t L = matchlen_u(data32, p, q, maxl);
                         if (L > bl) {
                             bl = L;
                             bd = p - q;
-                            tail = rd(p + bl - 3);
+                            tail = lds_rd32u(data32, p + bl - 3);
                         }
                     }
                 }
@@ -1127,25 +976,21 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 for (uint32_t i = i0 + t; i < i1; i += DF_NT) c4[i] = make_uint4(v, v, v, v);
                 const uint32_t p = 8 * i1 + t;
                 if (t < 16 && p < nb) S.cand[p] = (uint16_t)(p + 4 <= nb ? run_d : 0u);
-                if (RUNBACK) {  // (see run_e; the same alignbyte form as the rounds' forward test)
-                    constexpr uint32_t RP = 2 * DF_NT;
-                    const uint32_t bq = run_lo - RP + 4 * (uint32_t)t;
-                    if ((uint32_t)t < RP / 4 && bq >= run_d) {
-                        const uint32_t ia = (bq - run_d) >> 2;
-                        const uint32_t df = data32[bq >> 2] ^
-                                            __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], (run_lo - run_d) & 3);
-                        if (df) atomicMax(&S.sh[43], ((run_lo / RP + 1) << 16) | (bq + 4 - ((uint32_t)__builtin_clz(df) >> 3)));
-                    }
+                // (see run_e; the same alignbyte form as the rounds' forward test)
+                constexpr uint32_t RP = 2 * DF_NT;
+                const uint32_t bq = run_lo - RP + 4 * (uint32_t)t;
+                if ((uint32_t)t < RP / 4 && bq >= run_d) {
+                    const uint32_t ia = (bq - run_d) >> 2;
+                    const uint32_t df = data32[bq >> 2] ^
+                                        __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], (run_lo - run_d) & 3);
+                    if (df) atomicMax(&S.sh[43], ((run_lo / RP + 1) << 16) | (bq + 4 - ((uint32_t)__builtin_clz(df) >> 3)));
                 }
             }
             __syncthreads();
-            if (RUNLEN && run_lo != RUN_NONE) {
+            if (TERMRUN && run_lo != RUN_NONE) {
                 constexpr uint32_t RP = 2 * DF_NT;
-                run_e = run_lo;
-                if (RUNBACK) {
-                    const uint32_t et = __builtin_amdgcn_readfirstlane(S.sh[43]);
-                    run_e = (et >> 16) == run_lo / RP + 1 ? et & 0xFFFFu : max(run_lo - RP, (run_d + 3) & ~3u);
-                }
+                const uint32_t et = __builtin_amdgcn_readfirstlane(S.sh[43]);
+                run_e = (et >> 16) == run_lo / RP + 1 ? et & 0xFFFFu : max(run_lo - RP, (run_d + 3) & ~3u);
                 run_rcp = __builtin_amdgcn_rcpf((float)run_d);
             }
         }
@@ -1157,18 +1002,13 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // ---- parse walk: one DF_CHUNK-byte chunk per quad of lanes (the four walk in step and
         //      share the match-length compares, matchlen4); jumps over literal runs with the
         //      match bitmap, ORs token starts into tokmap (neighbouring chunks share words) -----
-        // DMX_DF_ADAPT: at level 2, a segment without a run (no round taken by the run
-        // continuation: short matches, text-like) is parsed in half-size chunks, twice the
-        // walkers; a segment with one keeps 258-byte chunks, whose matches reach the maximum
-        const uint32_t CH = (DMX_DF_ADAPT && level == 2 && !any_skip) ? (uint32_t)DF_CHUNK / 2 : (uint32_t)DF_CHUNK;
+        constexpr uint32_t CH = DF_CHUNK;
         const uint32_t nwalk = (nb - D + CH - 1) / CH;  // (the chunks start at D)
         // The walk exists twice in the 32 KiB level-2 kernel, chosen by a uniform branch: a segment
         // with a terminal run takes the one with the known lengths and the quad-wide literal
         // skip; every other segment (text, random) runs the plain walk, which both cost time.
         auto parse_walk = [&](auto runc) {
-            constexpr bool RUNW = decltype(runc)::value;
-            constexpr bool KNOWN = RUNW;  // this copy takes known lengths (the segment has RUNLEN)
-            constexpr bool LITSKIP = RUNW && DMX_DF_LITSKIP;
+            constexpr bool RUNW = decltype(runc)::value;  // the copy for a segment with a terminal run
             const uint32_t sub = t & 3;
             const bool lead = sub == 0;
             const uint32_t lo = D + (t >> 2) * CH;
@@ -1189,7 +1029,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             // matchlen4 of q against q - d; the length itself where it is known (a select on
             // the compared length: a known match compares nothing)
             auto len_at = [&](uint32_t q, uint32_t d, uint32_t maxl) -> uint32_t {
-                if (!KNOWN) return matchlen4(data32, q, q - d, maxl, sub);
+                if (!RUNW) return matchlen4(data32, q, q - d, maxl, sub);
                 const bool kn = known_len(q, d);
                 const uint32_t L = matchlen4(data32, q, q - d, kn ? 0u : maxl, sub);
                 return kn ? maxl : L;
@@ -1214,7 +1054,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 if (q >= hi || !m) {  // literals to the end of the word (or chunk)
                     uint32_t e = min((w + 1) * 32, hi);
                     tok |= bits_range(p, e, w);
-                    if (LITSKIP && e < hi) {
+                    if (RUNW && e < hi) {
                         // The quad looks ahead: lane sub inspects the (1 + sub)-th following
                         // bitmap word, clipped at hi.  The lanes before the first word with a
                         // match bit (or past hi) saw empty words: all literals, whose token bits
@@ -1284,14 +1124,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                             }
                         }
                     }
-                    if (!DF_SKIP && best == c) {  // one probe at c / k, k the largest divisor <= 8 (a
-                                                  // probe per k would serialize across lanes that differ in k)
-                        uint32_t k = 1;
-#pragma unroll
-                        for (uint32_t q = 2; q <= 8; q++) k = (c % q == 0) ? q : k;
-                        if (k > 1 && matchlen4(data32, p, p - c / k, ml, sub) >= L) best = c / k;
-                    }
-                    if (DF_SKIP && best == c) {
+                    if (best == c) {
                         // divisors c / k of the candidate, k <= 16 (the run-continuation rounds give
                         // every position of a run the same, possibly far, multiple of the period): lane sub takes the (sub + 1)-th
                         // largest k dividing c; one 16-byte compare round for the four, then full
@@ -1336,7 +1169,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             if (lead) S.lasttok[t >> 2] = (uint16_t)lastp;
         };
         if (level >= 2 && (uint32_t)t < 4 * nwalk) {
-            if constexpr (RUNLEN) {
+            if constexpr (TERMRUN) {
                 if (run_lo != RUN_NONE) parse_walk(std::true_type{});
                 else parse_walk(std::false_type{});
             } else
@@ -1453,15 +1286,6 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         const bool all_lit = tr_total == nb - D;
         if (all_lit) {
             if (t == 0) A.ntok[seg] = EM_ALL_LITERALS;
-            if (DMX_DF_HIST && DICT) {  // (the segment's own bytes start at D, any alignment)
-                for (uint32_t i = D + t; i < nb; i += DF_NT) atomicAdd(&S.hist[dbytes[i]], 1u);
-            } else if (DMX_DF_HIST)  // the literal histogram, four bytes per word
-                for (uint32_t i = t; 4 * i < nb; i += DF_NT) {
-                    const uint32_t x = data32[i];
-#pragma unroll
-                    for (uint32_t b = 0; b < 4; b++)
-                        if (4 * i + b < nb) atomicAdd(&S.hist[(x >> (8 * b)) & 0xFFu], 1u);
-                }
         } else {
             auto walk = [&](auto emit) {
                 uint32_t w = tr.w, m = tr.m, lit = 0, nl = 0;
@@ -1490,36 +1314,16 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             const uint32_t woff = block_excl_scan(nw, S.scan, &wtot);
             uint32_t* const dst = A.tok + seg * (uint64_t)A.tok_stride + woff;
             uint32_t j = 0;
-            walk([&](uint32_t v) {
-                dst[j++] = v;
-                if (DMX_DF_HIST) {  // the symbol counts the emission kernel codes with
-                    if (v >> 31) {
-                        atomicAdd(&S.hist[len_sym(((v >> 16) & 0xFFu) + 3)], 1u);
-                        atomicAdd(&S.hist[288 + dist_sym((v & 0x7FFFu) + 1)], 1u);
-                    } else {
-                        const uint32_t cnt = (v >> 24) & 3u;
-#pragma unroll
-                        for (uint32_t b = 0; b < 3; b++)
-                            if (b < cnt) atomicAdd(&S.hist[(v >> (8 * b)) & 0xFFu], 1u);
-                    }
-                }
-            });
+            walk([&](uint32_t v) { dst[j++] = v; });
             if (t == 0) A.ntok[seg] = wtot;
         }
         DMX_PHASE(A.dbg, seg, 11);
-        // every read of the segment's bytes is done (SWAP: nothing below writes LDS, and the
+        // every read of the segment's bytes is done (EARLY: nothing below writes LDS, and the
         // loop's closing barrier stands for this one)
-        if (EARLY && !SWAP) df_lds_barrier();
-        else if (!EARLY || DMX_DF_HIST) __syncthreads();
-        if (EARLY && !SWAP && staged) {  // the next segment's bytes: from the table to the image
-            const uint4* const u4 = reinterpret_cast<const uint4*>(U);
-            uint4* const d4 = reinterpret_cast<uint4*>(data32);
-#pragma unroll
-            for (int k = 0; k < SEG / (16 * DF_NT); k++) d4[t + k * DF_NT] = u4[t + k * DF_NT];
+        if constexpr (!EARLY) {
+            __syncthreads();
+            staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, data32);
         }
-        if (DMX_DF_HIST && t < (int)kDeflateHistWords)
-            A.tok[seg * (uint64_t)A.tok_stride + A.tok_stride - kDeflateHistWords + t] = S.hist[2 * t] | (S.hist[2 * t + 1] << 16);
-        if constexpr (!EARLY) staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, data32);
         DMX_PHASE(A.dbg, seg, 10);
     }
 }
@@ -1529,7 +1333,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
 // registers per lane, which amdgpu_waves_per_eu(8) asks for.
 // Persistent workgroups (as many as fit the GPU at once): workgroup b compresses segments
 // b, b + G, b + 2G, ... and loads each next segment while it works on the current one.
-// Early load with swapping buffers (DfSmem::SWAP): the image and the table are the two buffers of S.buf, and they
+// Early load (DfSmem::EARLY): the image and the table are the two buffers of S.buf, and they
 // swap roles on EVERY segment, staged or not (a workgroup-uniform base offset): the next
 // segment's bytes go into the current table, which is the next image.  A segment that was not
 // staged (an unaligned source, a short or a dictionary segment) loads into its image buffer at
@@ -1537,19 +1341,21 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
 // writes there and a staged load brings exactly SEG bytes.
 template <int SEG, bool L3, bool BATCH, bool DICT>
 __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SEG>& S) {
-    constexpr bool EARLY = DfSmem<SEG>::EARLY, SWAP = DfSmem<SEG>::SWAP;
+    constexpr bool EARLY = DfSmem<SEG>::EARLY;
     uint32_t staged = 0;  // the image already holds the segment's bytes
-    uint32_t iw = 0;      // (SWAP) the image's first word in S.buf: 0 or BW
-    if constexpr (SWAP) {
+    uint32_t iw = 0;      // (EARLY) the image's first word in S.buf: 0 or BW
+    if constexpr (EARLY) {
         const int t = df_tid();
         if (t < 64) S.buf[t >> 5][SEG / 4 + (t & 31)] = 0;  // (the first segment's barrier covers it)
     }
     for (uint64_t seg = blockIdx.x; seg < A.nseg; seg += gridDim.x) {
         deflate_segment<SEG, L3, BATCH, DICT>(A, S, seg, staged, iw);
         // the next segment reuses the LDS (not EARLY: and its prefetch has landed)
-        if constexpr (EARLY) df_lds_barrier();
-        else __syncthreads();
-        if constexpr (SWAP) iw = (uint32_t)DfSmem<SEG>::BW - iw;
+        if constexpr (EARLY) {
+            df_lds_barrier();
+            iw = (uint32_t)DfSmem<SEG>::BW - iw;
+        } else
+            __syncthreads();
     }
 }
 // BATCH: the segments come from the batch's segment table (df_seg_addr); the default
@@ -1585,26 +1391,14 @@ __global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 constexpr int EM_NW = 4;          // waves (segments) per 256-thread workgroup
 constexpr int EM_FLUSH = 256;     // staged whole words that trigger a flush to HBM
 constexpr int EM_STG = 576;       // staging words: EM_FLUSH + one block (256 x 36 bits) + slack
-// EmWave: the symbol counts share their LDS with the bit-staging window (1), and the emission
-// kernel asks for DMX_EM_OCC waves per SIMD (0: the compiler's choice)
-#ifndef DMX_EM_UNION
-#define DMX_EM_UNION 1
-#endif
-#ifndef DMX_EM_OCC
-#define DMX_EM_OCC 6
-#endif
 constexpr int EM_LIT = 288, EM_SYM = 320;  // lit/len symbols at [0, 288), distance at [288, 320)
 
 struct EmWave {
-#if DMX_EM_UNION
     // the symbol counts die with the code build; the bit-staging window starts after it
     union {
         uint32_t freq[EM_SYM];
         uint32_t stg[EM_STG];
     };
-#else
-    uint32_t freq[EM_SYM];
-#endif
     uint32_t code[EM_SYM];   // (len << 16) | bit-reversed code
     uint8_t len[EM_SYM];
     uint16_t rk[EM_SYM];     // per symbol slot: half-class | rank in it, then rank in its length;
@@ -1617,9 +1411,6 @@ struct EmWave {
     uint32_t kpre[2][20];    // per alphabet: members of the half-classes below k
     uint32_t start[2][16];   // per alphabet: first rank of code length l
     uint32_t next[2][16];    // per alphabet: first canonical code of length l
-#if !DMX_EM_UNION
-    uint32_t stg[EM_STG];
-#endif
 };
 
 struct EmCodes {
@@ -1927,35 +1718,26 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
 
     if (A.level != 0) {
         // ---- histogram ------------------------------------------------------------------
-        if (DMX_DF_HIST && !RAW && NH == 1) {  // the front kernel's counts
-            const uint32_t* const hs = A.tok + seg * (uint64_t)A.tok_stride + A.tok_stride - kDeflateHistWords;
-            for (int i = lane; i < (int)kDeflateHistWords; i += 64) {
-                const uint32_t x = hs[i];
-                W.freq[2 * i] = x & 0xFFFFu;
-                W.freq[2 * i + 1] = x >> 16;
-            }
-        } else {
-            for (int i = lane; i < EM_SYM; i += 64) W.freq[i] = 0;
-            wave_sync();
-            for (uint32_t h = 0; h < np; h++) {
-                const EmSrc S = part(h);
-                const uint32_t nblk = (S.ntok + 255) / 256;
-                for (uint32_t blk = 0; blk < nblk; blk++) {
-                    uint32_t v[4];
-                    S.load4(blk, v);
+        for (int i = lane; i < EM_SYM; i += 64) W.freq[i] = 0;
+        wave_sync();
+        for (uint32_t h = 0; h < np; h++) {
+            const EmSrc S = part(h);
+            const uint32_t nblk = (S.ntok + 255) / 256;
+            for (uint32_t blk = 0; blk < nblk; blk++) {
+                uint32_t v[4];
+                S.load4(blk, v);
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint32_t idx = blk * 256 + 4 * lane + j;
-                        if (idx >= S.ntok) continue;
-                        if (!S.raw && (v[j] >> 31)) {
-                            atomicAdd(&W.freq[len_sym(((v[j] >> 16) & 0xFFu) + 3)], 1u);
-                            atomicAdd(&W.freq[EM_LIT + dist_sym((v[j] & 0x7FFFu) + 1)], 1u);
-                        } else {
-                            const uint32_t cnt = S.count_of(v[j], idx);
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t idx = blk * 256 + 4 * lane + j;
+                    if (idx >= S.ntok) continue;
+                    if (!S.raw && (v[j] >> 31)) {
+                        atomicAdd(&W.freq[len_sym(((v[j] >> 16) & 0xFFu) + 3)], 1u);
+                        atomicAdd(&W.freq[EM_LIT + dist_sym((v[j] & 0x7FFFu) + 1)], 1u);
+                    } else {
+                        const uint32_t cnt = S.count_of(v[j], idx);
 #pragma unroll
-                            for (uint32_t i = 0; i < 4u; i++)
-                                if (i < cnt) atomicAdd(&W.freq[(v[j] >> (8 * i)) & 0xFFu], 1u);
-                        }
+                        for (uint32_t i = 0; i < 4u; i++)
+                            if (i < cnt) atomicAdd(&W.freq[(v[j] >> (8 * i)) & 0xFFu], 1u);
                     }
                 }
             }
@@ -2200,13 +1982,10 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
     if (lane == 0) A.sizes[seg] = total;
 }
 
-// RAW: level 1 (the input's bytes are the tokens) and level 0; else the front kernel's words
+// RAW: level 1 (the input's bytes are the tokens) and level 0; else the front kernel's words.
+// The kernel asks for six waves per SIMD.
 template <int SEG, bool RAW, bool BATCH = false>
-__global__ __launch_bounds__(64 * EM_NW)
-#if DMX_EM_OCC
-__attribute__((amdgpu_waves_per_eu(DMX_EM_OCC)))
-#endif
-void k_deflate_emit(DeflateArgs A) {
+__global__ __launch_bounds__(64 * EM_NW) __attribute__((amdgpu_waves_per_eu(6))) void k_deflate_emit(DeflateArgs A) {
     __shared__ EmWave Ws[EM_NW];
     const uint64_t seg = (uint64_t)blockIdx.x * EM_NW + (threadIdx.x >> 6);
     if (seg >= A.nseg) return;

@@ -57,11 +57,11 @@ struct DeflateArgs {
 
 // Token words per segment of the front kernel: a literal word covers 1-3 input bytes, a match
 // word at least 3, so at most seg / 2 words (one literal between every two 3-byte matches), plus
-// one partial literal word per thread's token range (1024 threads); the last kDeflateHistWords
-// words hold the segment's symbol histogram (320 counts as u16 pairs: lit/len symbols at 0..287,
-// distance symbols at 288..319, end of block not counted), which the emission kernel reads.
-constexpr uint32_t kDeflateHistWords = 160;
-constexpr uint32_t deflate_tok_stride(uint32_t seg) { return seg / 2 + 1024 + 64 + kDeflateHistWords; }
+// one partial literal word per thread's token range (1024 threads).  The remaining 224 words are
+// slack that nothing writes; they stay so that the token buffers' addresses and sizes do not move.
+constexpr uint32_t deflate_tok_stride(uint32_t seg) { return seg / 2 + 1248; }
+static_assert(deflate_tok_stride(32768) == 17632 && deflate_tok_stride(16384) == 9440,
+              "the token buffers' layout is fixed");
 
 // dict: the batch's segment table carries a preset dictionary (32 KiB segments, levels 2-3)
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, hipEvent_t ev0,

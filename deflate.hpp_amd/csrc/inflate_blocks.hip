@@ -40,14 +40,8 @@
 
 namespace dmx {
 
-#ifndef DMX_FB_SCAN_BITS
-#define DMX_FB_SCAN_BITS 16384
-#endif
-#ifndef DMX_FB_STEP
-#define DMX_FB_STEP 2048
-#endif
-constexpr uint32_t FB_SCAN_BITS = DMX_FB_SCAN_BITS;  // bit offsets tested per wavefront (2 KiB of stream)
-constexpr uint32_t FB_STEP = DMX_FB_STEP;            // offsets per prefilter step (32 per lane)
+constexpr uint32_t FB_SCAN_BITS = 16384;  // bit offsets tested per wavefront (2 KiB of stream)
+constexpr uint32_t FB_STEP = 2048;        // offsets per prefilter step (32 per lane)
 constexpr uint32_t FB_STAGE_WORDS = FB_SCAN_BITS / 32 + 128;  // + 4096 bits of header lookahead
 constexpr uint32_t FB_HITS = 96;          // candidates kept per scan chunk (true headers -- zlib at
                                           // memLevel 1-2 writes blocks of a few hundred bytes -- and
@@ -284,9 +278,7 @@ struct FbGlobalBits {
 // one reads on from HBM), and its precode table is an LDS column; both column-major, so the
 // lanes of a wave read distinct banks.  A candidate that is not a dynamic-block header a real
 // encoder could have written (fb_check_lengths) is marked FB_HIT_REJECT in place.
-#ifndef DMX_FBC_PER_WAVE
-#define DMX_FBC_PER_WAVE 64
-#endif
+constexpr int FBC_PER_WAVE = 64;    // candidates per wave
 constexpr uint32_t FBC_WORDS = 64;  // 2048 bits: the longest false candidates of a wave run ~1.2 Kbit
 typedef __attribute__((address_space(3))) uint32_t FbcLdsU32;
 typedef __attribute__((address_space(3))) uint8_t FbcLdsU8;
@@ -301,7 +293,7 @@ struct FbcBits {
         return __builtin_amdgcn_alignbit(col[64 * (i + 1)], col[64 * i], (uint32_t)(r & 31));
     }
 };
-// One lane per candidate, a wave per DMX_FBC_PER_WAVE candidates (its own range: a lane whose
+// One lane per candidate, a wave per FBC_PER_WAVE candidates (its own range: a lane whose
 // candidate is decided takes the range's next one once half the wave is idle, so a wave does
 // not wait for its longest candidate -- the test runs 48 symbols on average but ~230 at a
 // wave's slowest lane on C3).
@@ -312,18 +304,13 @@ struct FbcCol {
     FbGlobalBits g;
     __device__ uint32_t word(uint32_t k) const { return k < FBC_WORDS ? col[64 * k] : g.word(w0 + k); }
 };
-// DMX_FBK_DEFER (default): the tests that can only turn true once and stay true (a Kraft sum
+// The tests that can only turn true once and stay true (a Kraft sum
 // past 1, the sequence past HLIT + HDIST, the header past plim, an invalid code, a repeat with
 // nothing before it) are folded into one sticky flag per symbol and decided once per call, so
 // the serial symbol loop -- a true header's ~230 symbols set each wave's time -- carries fewer
 // instructions; a failing candidate runs on for at most `steps` - 1 symbols.
-#ifndef DMX_FBK_STEPS
-#define DMX_FBK_STEPS 32  // symbols per fbk_step call (the wave refills idle lanes between calls)
-#endif
-#ifndef DMX_FBK_DEFER
-#define DMX_FBK_DEFER 1
-#endif
-__device__ __forceinline__ void fbk_step_deferred(FbLengthCheck& c, const FbcCol& src, int steps) {
+constexpr int FBK_STEPS = 32;  // symbols per fbk_step call (the wave refills idle lanes between calls)
+__device__ __forceinline__ void fbk_step(FbLengthCheck& c, const FbcCol& src, int steps) {
     if (c.st != FBK_RUN) return;
     uint32_t i = c.i, prev = c.prev, kl = c.kl, kd = c.kd, nd = c.nd, nb = c.nb, used = c.used, wi = c.wi;
     uint64_t buf = c.buf;
@@ -369,48 +356,6 @@ __device__ __forceinline__ void fbk_step_deferred(FbLengthCheck& c, const FbcCol
     if (bad || i > total || kl > 32768 || kd > 32768 || used > c.plim) c.st = FBK_FAIL;
     else if (i == total) c.st = eob && kl == 32768 && (kd == 32768 || nd <= 1) ? FBK_PASS : FBK_FAIL;
 }
-__device__ __forceinline__ void fbk_step(FbLengthCheck& c, const FbcCol& src, int steps) {
-    if (DMX_FBK_DEFER) {
-        fbk_step_deferred(c, src, steps);
-        return;
-    }
-    for (int k = 0; k < steps; k++) {
-        if (c.st != FBK_RUN) break;
-        if (c.i >= c.total) {
-            c.st = c.eob && c.kl == 32768 && (c.kd == 32768 || c.nd <= 1) ? FBK_PASS : FBK_FAIL;
-            break;
-        }
-        if (c.nb < 32) {  // refill: at least 32 bits stay in the buffer (a symbol takes <= 14)
-            c.buf |= (uint64_t)src.word(c.wi) << c.nb;
-            c.wi++;
-            c.nb += 32;
-        }
-        const uint32_t v = (uint32_t)c.buf;
-        uint32_t sym, len;
-        c.decode(v, &sym, &len);
-        const uint32_t eb = sym == 16 ? 2u : sym == 17 ? 3u : sym == 18 ? 7u : 0u;
-        const uint32_t rb = sym == 16 ? 3u : sym == 17 ? 3u : sym == 18 ? 11u : 1u;
-        const uint32_t run = rb + ((v >> len) & ((1u << eb) - 1u));
-        const uint32_t val = sym < 16 ? sym : sym == 16 ? c.prev : 0u;
-        const uint32_t cons = len + eb;
-        c.buf >>= cons;
-        c.nb -= cons;
-        c.used += cons;
-        // lengths [i, i + run): split at nlit
-        const uint32_t a = c.i < c.nlit ? min(c.i + run, c.nlit) - c.i : 0u;
-        const uint32_t b = run - a;
-        const uint32_t sh = 15 - (val ? val : 15u);
-        c.kl += val ? a << sh : 0u;
-        c.kd += val ? b << sh : 0u;
-        c.nd += val ? b : 0u;
-        c.eob |= val && c.i <= 256 && 256 < c.i + a;
-        const bool bad = !len || (sym == 16 && c.i == 0) || c.i + run > c.total || c.kl > 32768 || c.kd > 32768 ||
-                         c.used > c.plim;
-        c.prev = val;
-        c.i += run;
-        if (bad) c.st = FBK_FAIL;
-    }
-}
 // A candidate that passes (and every stored-header hit) is also appended to keep (host memory
 // mapped into the device; *nkeep counts, entries past keep_cap are dropped): the host reads the
 // accepted starts -- a few hundred -- instead of the whole candidate list.
@@ -418,7 +363,7 @@ __global__ __launch_bounds__(64) void k_fb_check(const uint32_t* in_words, uint6
                                                   uint64_t* list, const uint64_t* pcount, unsigned long long* ph,
                                                   uint64_t* keep, uint32_t* nkeep, uint32_t keep_cap) {
     const uint64_t count = *pcount;  // (the grid is sized for the most the scan could list)
-    if ((uint64_t)blockIdx.x * DMX_FBC_PER_WAVE >= count) return;
+    if ((uint64_t)blockIdx.x * FBC_PER_WAVE >= count) return;
     auto accept = [&](uint64_t e) {
         if (!keep) return;
         const uint32_t k = atomicAdd(nkeep, 1u);
@@ -435,8 +380,8 @@ __global__ __launch_bounds__(64) void k_fb_check(const uint32_t* in_words, uint6
     ck.tab = (FbcLdsU8*)(tabs) + 4 * lane;
     FbcCol src{col, in_words, 0, g};
     bool busy = false;
-    uint64_t nxt = (uint64_t)blockIdx.x * DMX_FBC_PER_WAVE;
-    const uint64_t end = min(count, nxt + DMX_FBC_PER_WAVE);
+    uint64_t nxt = (uint64_t)blockIdx.x * FBC_PER_WAVE;
+    const uint64_t end = min(count, nxt + FBC_PER_WAVE);
     uint64_t idx = 0, e = 0;
     uint64_t c_ref = 0, c_step = 0, n_out = 0, n_busy = 0, tl = ph ? clock64() : 0;
     for (;;) {
@@ -499,7 +444,7 @@ __global__ __launch_bounds__(64) void k_fb_check(const uint32_t* in_words, uint6
         n_out++;
         n_busy += (uint64_t)__popcll(bm);
         if (busy) {
-            fbk_step(ck, src, DMX_FBK_STEPS);
+            fbk_step(ck, src, FBK_STEPS);
             if (ck.st != FBK_RUN) {
                 if (ck.st == FBK_FAIL) list[idx] = e | FB_HIT_REJECT;
                 else accept(e);
@@ -820,23 +765,11 @@ __global__ __launch_bounds__(64) void k_fb_decode(FbDecodeArgs A) {
 // unit 0 -- makes wave 0 decode the whole unit with fb_serial instead, so results and error
 // codes are the serial decoder's.
 // ---------------------------------------------------------------------------------------
-#ifndef DMX_FBP_NT
-#define DMX_FBP_NT 1024
-#endif
-#ifndef DMX_FBP_IN
-#define DMX_FBP_IN 14336
-#endif
-constexpr int FBP_NT = DMX_FBP_NT;
-constexpr uint32_t FBP_IN = DMX_FBP_IN;  // staged words (a block body of up to ~56 KB: zlib's
-                                      // blocks of 16 K symbols at up to ~27 bits each)
-#ifndef DMX_FBP_MINBITS
-#define DMX_FBP_MINBITS 96
-#endif
-constexpr uint32_t FBP_MINBITS = DMX_FBP_MINBITS;  // shortest range a lane decodes
-#ifndef DMX_FBP_WARM
-#define DMX_FBP_WARM 448
-#endif
-constexpr uint32_t FBP_WARM = DMX_FBP_WARM;  // warm-up bits before a range
+constexpr int FBP_NT = 1024;
+constexpr uint32_t FBP_IN = 14336;  // staged words (a block body of up to ~56 KB: zlib's
+                                    // blocks of 16 K symbols at up to ~27 bits each)
+constexpr uint32_t FBP_MINBITS = 96;  // shortest range a lane decodes
+constexpr uint32_t FBP_WARM = 448;    // warm-up bits before a range
 constexpr uint32_t TK_NOP = 4;         // a fixed block's end of block + the next fixed header
 constexpr int FBP_ROUNDS = 1024;  // a settle cascade (data that re-synchronises slowly) still
                                    // beats the serial decoder by far
@@ -1580,9 +1513,7 @@ constexpr uint32_t FBR_FINAL = 0x80000000u;
 constexpr uint32_t FBU_PS = 16384;  // piece positions (32-bit entries: 64 KiB of LDS)
 constexpr uint32_t FBU_R = 32768;   // resolved ring (16-bit entries: 64 KiB)
 constexpr uint32_t FBU_LIT = 1, FBU_MATCH = 2, FBU_STORED = 3;
-#ifndef DMX_FBU_SPREAD
-#define DMX_FBU_SPREAD 40
-#endif
+constexpr uint32_t FBU_SPREAD = 40;  // see `spread` in k_fb_units
 __global__ __launch_bounds__(FBR_NT) void k_fb_units(FbReplayArgs A) {
     __shared__ __attribute__((aligned(16))) uint32_t C[FBU_PS];
     __shared__ __attribute__((aligned(16))) uint16_t R[FBU_R];
@@ -1686,8 +1617,8 @@ __global__ __launch_bounds__(FBR_NT) void k_fb_units(FbReplayArgs A) {
         const uint32_t bend = obase + T;
         // one token per lane costs each wave its longest token; spreading the positions costs
         // ~16 stores per thread plus a binary search: spread when the waves' longest tokens
-        // average more than DMX_FBU_SPREAD positions (image rows, runs)
-        const bool spread = smax > (uint32_t)DMX_FBU_SPREAD * NW;
+        // average more than FBU_SPREAD positions (image rows, runs)
+        const bool spread = smax > FBU_SPREAD * NW;
         if (spread) {
             Gw[t] = w;
             Go[t] = go;
@@ -1869,14 +1800,8 @@ __global__ __launch_bounds__(FB_TNT) void k_fb_tails(const uint16_t* __restrict_
 //   k_fb_final      every output byte: an image byte, or its marker's window entry.
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t FB_WLIT = 0x80000000u;
-#ifndef DMX_FB_HOPS
-#define DMX_FB_HOPS 8
-#endif
-constexpr int FB_HOPS = DMX_FB_HOPS;
-#ifndef DMX_FB_WIN_ROUNDS
-#define DMX_FB_WIN_ROUNDS 2
-#endif
-constexpr uint32_t FB_WIN_ROUNDS = DMX_FB_WIN_ROUNDS;  // jump rounds launched (k_fb_final finishes the chains)
+constexpr int FB_HOPS = 8;
+constexpr uint32_t FB_WIN_ROUNDS = 2;  // jump rounds launched (k_fb_final finishes the chains)
 constexpr uint32_t FB_WIN_BLK = 4096;  // window entries per k_fb_win_init workgroup
 __global__ __launch_bounds__(256) void k_fb_win_init(const uint16_t* __restrict__ img,
                                                      const uint64_t* __restrict__ offs,
@@ -2424,8 +2349,8 @@ hipError_t launch_fb_compact(const uint32_t* in_words, uint64_t misalign, uint64
     hipLaunchKernelGGL(k_fb_compact, dim3((uint32_t)((nchunks + 255) / 256)), dim3(256), 0, st,
                        counts, offs, hits, nchunks, list);
     if (max_count) {
-        // a wave per DMX_FBC_PER_WAVE candidates: its first 64, then refills as its lanes finish
-        const uint32_t g = (uint32_t)((max_count + DMX_FBC_PER_WAVE - 1) / DMX_FBC_PER_WAVE);
+        // a wave per FBC_PER_WAVE candidates: its first 64, then refills as its lanes finish
+        const uint32_t g = (uint32_t)((max_count + FBC_PER_WAVE - 1) / FBC_PER_WAVE);
         hipLaunchKernelGGL(k_fb_check, dim3(g), dim3(64), 0, st, in_words, misalign, n, list, pcount, ph, keep, nkeep,
                            keep_cap);
     }

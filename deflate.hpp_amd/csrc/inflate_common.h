@@ -910,10 +910,7 @@ __device__ uint32_t inflate_blocks(BR& br, Tables& T, Sink& sk, bool rfc, bool s
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) const u32x4 GUint4;  // global, not flat: a flat
                                                                // load also counts in lgkmcnt
-#ifndef DMX_LN_RING_LOW
-#define DMX_LN_RING_LOW 16
-#endif
-constexpr uint32_t LN_RING_LOW = DMX_LN_RING_LOW;  // top up when fewer words than this are buffered
+constexpr uint32_t LN_RING_LOW = 16;  // top up when fewer words than this are buffered
 
 struct LaneIn {
     GUint4* blk;     // the candidate's first 16-byte quad: all positions below are 32-bit,

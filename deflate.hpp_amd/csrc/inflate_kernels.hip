@@ -315,19 +315,11 @@ __global__ __launch_bounds__(IF_NT) void k_inflate_segments(InflateArgs A) {
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t PJ_LIT = 0x8000u;
 constexpr int PJ_ROUNDS = 64;
-#ifndef PJ_MINBITS_
-#define PJ_MINBITS_ 192u  // (256: +7 % on text, 384: +14 %; measured with the 320-bit warm-up)
-#endif
-constexpr uint32_t PJ_MINBITS = PJ_MINBITS_;  // shortest range (bits) a lane decodes
-#ifndef PJ_LIST_NT
-#define PJ_LIST_NT 512  // lanes per workgroup of the heavy route (k_inflate_pj_list)
-#endif
-#ifndef PJ_MINBITS_1K
-#define PJ_MINBITS_1K 128u  // shortest range with 1024 lanes
-#endif
-#ifndef PJ_WARM
-#define PJ_WARM 320u  // warm-up bits before a range's first pass (128: +25 % on text, 512: +1 %)
-#endif
+// shortest range (bits) a lane decodes (256: +7 % on text, 384: +14 %; measured with the 320-bit warm-up)
+constexpr uint32_t PJ_MINBITS = 192u;
+constexpr int PJ_LIST_NT = 512;  // lanes per workgroup of the heavy route (k_inflate_pj_list)
+constexpr uint32_t PJ_MINBITS_1K = 128u;  // shortest range with 1024 lanes
+constexpr uint32_t PJ_WARM = 320u;  // warm-up bits before a range's first pass (128: +25 % on text, 512: +1 %)
 
 template <int SEG, int NT>
 struct PjSmem {
@@ -1395,9 +1387,6 @@ __global__ __launch_bounds__(IF_NT) void k_inflate_serial(InflateArgs A, int cou
 // Headers, stored blocks and the block loop stay on wave 0 (inflate_blocks); the other waves
 // wait at the workgroup barrier and join every Huffman block (decode_block below).
 // ---------------------------------------------------------------------------------------
-#ifndef DMX_SW_DIAG
-#define DMX_SW_DIAG 0  // developer aid: the cycle slots 0-3 count walk attempts / successes / rounds / failures
-#endif
 constexpr int SW_NT = 1024;
 constexpr uint32_t SW_R = 2048;        // bit offsets per region
 constexpr uint32_t SW_LMAX = 11;       // doubling levels for 2048 one-bit tokens
@@ -1797,7 +1786,7 @@ __device__ __attribute__((noinline)) void sw_block(SwSmem& S, GlbU32* w, uint64_
     uint64_t tc = timed ? __builtin_amdgcn_s_memtime() : 0;
     uint64_t cy[6] = {0, 0, 0, 0, 0, 0};
     auto stamp = [&](int k) {
-        if (timed && (!DMX_SW_DIAG || k >= 4)) {
+        if (timed) {
             const uint64_t t1 = __builtin_amdgcn_s_memtime();
             cy[k] += t1 - tc;
             tc = t1;
@@ -1822,17 +1811,6 @@ __device__ __attribute__((noinline)) void sw_block(SwSmem& S, GlbU32* w, uint64_
             const uint32_t r = sw_walk(S, w, nwords, end_bytes, p, pos, &np, &nt, &rounds, timed, walk & 0xFFFFu,
                                        walk >> 16);
             stamp(4);
-#ifdef DMX_SW_TRACE
-            if (t == 0 && pos + 40000 > DMX_SW_TRACE && pos < DMX_SW_TRACE + 1000)
-                printf("walk p %llu pos %llu -> r %u np %llu nt %u rounds %u\n", (unsigned long long)p,
-                       (unsigned long long)pos, r, (unsigned long long)np, nt, rounds);
-#endif
-#if DMX_SW_DIAG
-            cy[0] += 1;                           // attempts
-            cy[1] += r != 2;                      // successes
-            cy[2] += rounds < 1000 ? rounds : 0;  // rounds of the converged ones
-            cy[3] += rounds >= 1000;              // not converged
-#endif
             if (r != 2) {
                 pos += nt;
                 p = np;
@@ -2025,10 +2003,6 @@ __device__ __attribute__((noinline)) void sw_block(SwSmem& S, GlbU32* w, uint64_
         }
         __syncthreads();
         stamp(3);
-#ifdef DMX_SW_TRACE
-        if (t == 0 && pos + 40000 > DMX_SW_TRACE && pos < DMX_SW_TRACE + 1000)
-            printf("dbl p %llu pos %llu tot %u C %u nmem %u\n", (unsigned long long)p, (unsigned long long)pos, tot, C, nmem);
-#endif
         pos += tot;
         p = nextp;
         flush_if();

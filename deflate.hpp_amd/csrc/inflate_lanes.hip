@@ -7,10 +7,9 @@
 // area; 32 segments per one-wave workgroup = 40 KiB, four workgroups per CU): see LN_REGION.
 // Phases of a workgroup:
 //   1. each lane reads its block header (BTYPE; stored segments are handled right there);
-//   2. the wave builds every dynamic segment's precode table in turn (ln_coop_table: ballot
-//      counts, canonical order, one table entry per lane);
+//   2. each lane builds its dynamic segment's precode table (ln_lane_pretab);
 //   3. each lane decodes its code-length sequence once into bytes (branch-free steps);
-//   4. the wave builds every segment's 9-bit lit/len and 6-bit distance tables in turn;
+//   4. each lane builds its segment's 9-bit lit/len and 6-bit distance tables (ln_lane_table);
 //   5. each lane decodes its tokens: a 64-bit window per symbol from a per-lane LDS ring of
 //      the stream (no refill branch), table lookups, select-based token logic.  The decoded
 //      tokens go to HBM as 32-bit words:
@@ -33,7 +32,7 @@
 // parallel (4 bytes per iteration when d >= 4), long or self-dependent matches are copied by the
 // whole wave in token order (periodic copy out[o + i] = out[o - d + (i mod d)], as the
 // reference's byte-serial copy inflate.hpp:268-270); then all waves put the window at j * slot
-// with 16-byte stores (a long periodic copy at the segment's end goes straight to HBM).
+// with 16-byte stores.
 #include "../../include/dmx.h"
 #include "dmx_device.h"
 #include "dmx_internal.h"
@@ -62,58 +61,26 @@ typedef uint64_t u64_unaligned __attribute__((aligned(1)));
 typedef uint32_t u32_unaligned __attribute__((aligned(1)));
 typedef uint16_t u16_unaligned __attribute__((aligned(1)));
 static_assert(LN_HDR_QUADS * 16 <= LN_LENS, "header quads overlap the code lengths");
-#ifndef DMX_LN_LANES
-#define DMX_LN_LANES 32
-#endif
 // segments per 64-thread workgroup: 32 x 1280 B = 40 KiB of LDS, four workgroups per CU, one
 // decoding wave per SIMD holding 32 segments.  The branch-free token step is VALU-issue-bound,
 // so one wave of 32 segments beats two of 16 (1 GiB text inflate 12.3 -> 10.9 ms); the
 // table builds take the other half of the wave's lanes.
-constexpr uint32_t LN_LANES = DMX_LN_LANES;
-// token step: a literal followed by a literal decodes both (the step's second table lookup is the
-// distance code after a length, else the next lit/len symbol)
-#ifndef DMX_LN_PAIR
-#define DMX_LN_PAIR 1
-#endif
-// lane tables: the code-length words read ahead of their use (1) or at it (0)
-#ifndef DMX_LN_PREF
-#define DMX_LN_PREF 1
-#endif
-// precode tables: one per lane, all segments at once (1), or built by the whole wave one segment
-// after the other (0, ln_coop_table)
-#ifndef DMX_LN_PRETAB
-#define DMX_LN_PRETAB 1
-#endif
+constexpr uint32_t LN_LANES = 32;
 // resolve workgroup: RS_NT threads around one window.  Wave 0 runs the token steps, the
 // workgroup fills periodic copies of >= RS_BIG bytes (repeat, zeros, image rows: segments of at
 // most RS_FOLLOW token words) and copies the window out.  A 32 KiB window allows five workgroups
 // per CU: with one wave each, those copies ran at 1.25 waves per SIMD, latency-bound.
-#ifndef DMX_RS_NT
-#define DMX_RS_NT 256
-#endif
-#ifndef DMX_RS_BIG
-#define DMX_RS_BIG 2048
-#endif
-#ifndef DMX_RS_FOLLOW
-#define DMX_RS_FOLLOW 1024
-#endif
-constexpr uint32_t RS_FOLLOW = DMX_RS_FOLLOW;
-#ifndef DMX_RS_SPLIT
-#define DMX_RS_SPLIT 1
-#endif
+constexpr uint32_t RS_NT = 256;
+constexpr uint32_t RS_BIG = 2048;
+constexpr uint32_t RS_FOLLOW = 1024;
 // (NT = 64) the segment's last token, a periodic copy, written straight to HBM (1) or through
-// the window (0; measured faster: repeat inflate 0.629 vs 0.655 ms, zeros 0.468 vs 0.495 ms)
+// the window (0; measured faster: repeat inflate 0.629 vs 0.655 ms, zeros 0.468 vs 0.495 ms).
+// Kept as a switch: without this dead path the compiler lays out k_inflate_resolve differently.
 #ifndef DMX_LN_DIRECT
 #define DMX_LN_DIRECT 0
 #endif
-constexpr uint32_t RS_NT = DMX_RS_NT;
-constexpr uint32_t RS_BIG = DMX_RS_BIG;
 static_assert(RS_NT % 64 == 0 && RS_NT <= 1024, "resolve workgroup");
-constexpr bool kRsSplit = DMX_RS_SPLIT && RS_NT > 64;
-#ifndef DMX_RS_TICKET_WG
-#define DMX_RS_TICKET_WG 5
-#endif
-constexpr uint32_t RS_TICKET_WG = DMX_RS_TICKET_WG;  // one-wave resolve workgroups per CU
+constexpr uint32_t RS_TICKET_WG = 5;  // one-wave resolve workgroups per CU
 
 __constant__ const uint8_t kLnPerm[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5,
                                           11, 4,  12, 3, 13, 2, 14, 1, 15};
@@ -135,74 +102,6 @@ struct LaneArgs {
 __device__ __forceinline__ uint32_t ln_lit_entry(uint32_t s, uint32_t l) {
     if (s >= 257 && s <= 285) return 0x8000u | (l << 11) | (len_extra(s) << 8) | (len_base(s) - 3);
     return (l << 11) | s;
-}
-
-// Canonical decode table of one code, built by the whole wavefront (RFC 1951 3.2.2; the
-// reference builds a bit-trie, FlatHuffmanTree::construct common.hpp:104-145).  lens(s) gives
-// the code length of symbol s < nsym (0 = unused); table[x] for every B-bit index x (the next B
-// stream bits, LSB first) decodes the code that is a prefix of x.  Steps: per-length counts by
-// ballots, canonical first codes, symbols in canonical order into `order`, then each lane fills
-// entries x = lane + 64 k: the code length is the first l with (rev(x) >> (B - l)) below that
-// length's limit (canonical codes are monotone, so the test is a count, no search), the symbol
-// order[base[l] + code].  Returns false unless the code is complete with all lengths <= B.
-template <int B, class Lens, class Order, class Put>
-__device__ __forceinline__ bool ln_coop_table(uint32_t nsym, Lens lens, Order order, Put put) {
-    const uint32_t lane = lane_id();
-    const uint64_t lt = (1ull << lane) - 1ull;
-    uint32_t cnt[B + 1];
-#pragma unroll
-    for (int l = 0; l <= B; l++) cnt[l] = 0;
-    bool bad = false;
-    for (uint32_t c = 0; c < nsym; c += 64) {
-        const uint32_t s = c + lane;
-        const uint32_t L = s < nsym ? lens(s) : 0u;
-        bad |= __ballot(L > (uint32_t)B) != 0;
-#pragma unroll
-        for (int l = 1; l <= B; l++) cnt[l] += (uint32_t)__popcll(__ballot(L == (uint32_t)l));
-    }
-    uint32_t kraft = 0;
-#pragma unroll
-    for (int l = 1; l <= B; l++) kraft += cnt[l] << (B - l);
-    if (bad || kraft != (1u << B)) return false;
-    uint32_t limit[B + 1], base[B + 1], run[B + 1];
-    uint32_t first = 0, off = 0;
-#pragma unroll
-    for (int l = 1; l <= B; l++) {
-        first = (first + cnt[l - 1]) << 1;  // cnt[0] = 0
-        limit[l] = first + cnt[l];
-        base[l] = off - first;  // order index = base + code (mod 2^32)
-        run[l] = off;
-        off += cnt[l];
-    }
-    for (uint32_t c = 0; c < nsym; c += 64) {
-        const uint32_t s = c + lane;
-        const uint32_t L = s < nsym ? lens(s) : 0u;
-#pragma unroll
-        for (int l = 1; l <= B; l++) {
-            const uint64_t b = __ballot(L == (uint32_t)l);
-            if (L == (uint32_t)l) order(run[l] + (uint32_t)__popcll(b & lt), s, 1);
-            run[l] += (uint32_t)__popcll(b);
-        }
-    }
-    wave_sync();
-    static_assert(B >= 6, "one table entry per lane at least");
-#pragma unroll
-    for (uint32_t k = 0; k < (1u << B) / 64; k++) {
-        const uint32_t x = lane + 64 * k;
-        const uint32_t v = bitrev(x, B);
-        uint32_t idx = 0, len = 0;
-#pragma unroll
-        for (int l = B; l >= 1; l--) {
-            const uint32_t p = v >> (B - l);
-            if (p < limit[l]) {
-                idx = base[l] + p;
-                len = (uint32_t)l;
-            }
-        }
-        put(x, order(idx, 0, 0), len);
-    }
-    wave_sync();
-    return true;
 }
 
 // Per-lane canonical tables (one lane per segment, all segments of the wave at once).  Nine 9-bit
@@ -248,17 +147,11 @@ __device__ __forceinline__ bool ln_lane_table(uint16_t* T, const Pk9& cnt, uint3
 #pragma unroll 4
     for (uint32_t w = 0; w < NW / 2; w++) T64w[(w + lane) & (NW / 2 - 1)] = m4;
     // symbols below NL (a multiple of 8, < nsym): entry (L << lsh) | sym, no bound test
-    // (DMX_LN_PREF: each word read one iteration ahead, its LDS latency behind the 8 symbols)
-#if DMX_LN_PREF
+    // (each word read one iteration ahead, its LDS latency behind the 8 symbols)
     uint32_t xn = word(0);
-#endif
     for (uint32_t k = 0; 8 * k < (uint32_t)NL; k++) {
-#if DMX_LN_PREF
         const uint32_t x = xn;
         xn = word(k + 1);  // (k + 1 <= NL / 8: the next loop's first word)
-#else
-        const uint32_t x = word(k);
-#endif
 #pragma unroll
         for (uint32_t i = 0; i < 8; i++) {
             const uint32_t sym = 8 * k + i, L = (x >> (4 * i)) & 15u;
@@ -270,11 +163,7 @@ __device__ __forceinline__ bool ln_lane_table(uint16_t* T, const Pk9& cnt, uint3
         }
     }
     for (uint32_t k = NL / 8; 8 * k < nsym; k++) {
-#if DMX_LN_PREF
         const uint32_t x = k == NL / 8 && NL > 0 ? xn : word(k);
-#else
-        const uint32_t x = word(k);
-#endif
 #pragma unroll
         for (uint32_t i = 0; i < 8; i++) {
             const uint32_t sym = 8 * k + i, L = (x >> (4 * i)) & 15u;
@@ -529,30 +418,10 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
     }
     const bool huff = seg_lane && !flags && (btype == 1 || btype == 2);
     const uint32_t dyn_mask = (uint32_t)__ballot(huff && btype == 2);
-    // ---- precode tables of the dynamic segments, built by the wave (7-bit, u8 entries) -------
-    uint32_t bad_mask = 0;
-#if DMX_LN_PRETAB
-    // one table per lane, all segments at once
+    // ---- precode tables of the dynamic segments (7-bit, u8 entries): one table per lane, all
+    //      segments at once ---------------------------------------------------------------------
     if (huff && btype == 2 && !ln_lane_pretab(PRE, pl)) flags |= SEGF_EXOTIC;
     wave_sync();
-#else
-    for (uint32_t m = dyn_mask; m; m &= m - 1) {
-        const uint32_t s = (uint32_t)__builtin_ctz(m);
-        const uint64_t pls = ((uint64_t)__builtin_amdgcn_readlane((int)(uint32_t)(pl >> 32), s) << 32) |
-                             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pl, s);
-        uint8_t* const ord = lds + s * LN_REGION + LN_DIST;  // canonical order scratch
-        uint8_t* const tab = SH + s * LN_PRE_BYTES;
-        const bool ok = ln_coop_table<7>(
-            19u, [&](uint32_t sym) { return (uint32_t)(pls >> (3 * sym)) & 7u; },
-            [&](uint32_t i, uint32_t sym, int wr) -> uint32_t {
-                if (wr) { ord[i] = (uint8_t)sym; return 0u; }
-                return ord[i];
-            },
-            [&](uint32_t x, uint32_t sym, uint32_t len) { tab[x] = (uint8_t)(sym | (len << 5)); });
-        if (!ok) bad_mask |= 1u << s;
-    }
-#endif
-    if (seg_lane && ((bad_mask >> lane) & 1u)) flags |= SEGF_EXOTIC;
     if (dbg) dbg[1] = __builtin_amdgcn_s_memtime();
 
     // ---- code lengths of the dynamic segments, decoded once into bytes (lane-serial) ------------
@@ -640,9 +509,7 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
         uint32_t* const PD = reinterpret_cast<uint32_t*>(R + LN_DIST);             // words 32..39
         const uint32_t* const LW = reinterpret_cast<const uint32_t*>(R + LN_LENS);
         Pk9 cl = {0ull, 0u}, cd = {0ull, 0u};
-#if DMX_LN_PREF
 #pragma unroll 8
-#endif
         for (uint32_t k = 0; k < 40; k++) {
             // fixed code (RFC 1951 3.2.6): 8 (0..143), 9 (144..255), 7 (256..279), 8 (280..287), 5
             const uint32_t fw = k < 18 ? 0x88888888u : k < 32 ? 0x99999999u : k < 35 ? 0x77777777u
@@ -722,9 +589,6 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             win = window_at(bp, ring2[pr & 15], ring2[(pr + 1) & 15]);
         }
         auto step = [&]() -> bool {
-#ifdef DMX_LN_COUNT
-            n_iter++;  // diagnostic build: steps per lane (DMX_PHASES slot 8)
-#endif
             const uint32_t pr = bp >> 6;
             const uint64_t nq0 = ring2[(pr + 1) & 15], nq1 = ring2[(pr + 2) & 15];
             // lit/len symbol, then the distance decoded from the same window (used for lengths)
@@ -735,26 +599,18 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             const uint32_t L = (e & 255) + 3 + ((uint32_t)(win >> cl) & ((1u << ex) - 1u));
             const uint32_t n1 = cl + ex;
             const uint64_t dwin = win >> n1;
-#if DMX_LN_PAIR
             // the second lookup from the same window: the distance code after a length, else the
             // next lit/len symbol -- a literal after a literal is consumed in the same step
             // (literal pairs at the cost of one step)
             const uint32_t de = lut16(isl ? LN_DIST + 2 * ((uint32_t)dwin & 63u) : 2 * ((uint32_t)dwin & 511u));
-#else
-            const uint32_t de = lut16(LN_DIST + 2 * ((uint32_t)dwin & 63u));
-#endif
             const uint32_t dcl = (de >> 8) & 7, ds = de & 31;
             const uint32_t dx = dist_extra(ds);
             const uint32_t d = dist_base(ds) + ((uint32_t)(dwin >> dcl) & ((1u << dx) - 1u));
             const uint32_t sym = e & 511;
-#if DMX_LN_PAIR
             const uint32_t sym2 = de & 511, cl2 = (de >> 11) & 15;
             const bool lit2 = !isl & (sym < 256) & ((de & 0x8000u) == 0u) & (sym2 < 256) &
                               (outpos + 2 <= CAP) & (!SPLIT | (outpos + 1 != HALF));
             const uint32_t c = n1 + (isl ? dcl + dx : (lit2 ? cl2 : 0u));  // 1 .. 33 bits
-#else
-            const uint32_t c = n1 + (isl ? dcl + dx : 0u);  // 1 .. 33 bits
-#endif
             const uint64_t ext = window_at(bp + 64, nq0, nq1);
             win = (win >> c) | ((ext << 1) << (63 - c));
             bp += c;
@@ -775,7 +631,6 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             const bool mt = isl & !far & ok;
             const bool lt = lit & ok;
             const bool prod = lt | mt;
-#if DMX_LN_PAIR
             // nl literal bytes lb (1 or 2); a pending run of 2 takes the first of a pair and a
             // new run starts with the second (lsplit)
             const bool lt2 = lt & lit2;
@@ -803,23 +658,6 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             pd = prod ? npd : pd;
             pk = prod ? (lt ? 1u : 2u) : pk;
             outpos += prod ? (lt ? nl : L) : 0u;
-#else
-            const bool lcont = lt & (pk == 1u) & (pd < 3u);
-            const bool mcont = mt & (pk == 2u) & (pd == d) & (pa + L <= 0xFFFFu);
-            const bool cont = lcont | mcont;
-            const bool emit = prod & !cont & (pk != 0u);
-            const uint32_t ew = pk == 1u ? (pd << 24) | pa : 0x80000000u | (pa << 15) | (pd - 1u);
-            const uint32_t a_cont = lcont ? (pa | (sym << (8 * pd))) : (pa + L);
-            const uint32_t a_new = lt ? sym : L;
-            const uint32_t d_cont = lcont ? pd + 1u : pd;
-            const uint32_t d_new = lt ? 1u : d;
-            const uint32_t npa = cont ? a_cont : a_new;
-            const uint32_t npd = cont ? d_cont : d_new;
-            pa = prod ? npa : pa;
-            pd = prod ? npd : pd;
-            pk = prod ? (lt ? 1u : 2u) : pk;
-            outpos += prod ? (lt ? 1u : L) : 0u;
-#endif
             // queue of 4 token words (shift register), one 16-byte store per 4 words
             q0 = emit ? q1 : q0;
             q1 = emit ? q2 : q1;
@@ -846,21 +684,9 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
         };
         static_assert(LN_PERIOD == 3, "steps per period below");
         for (;;) {
-#ifdef DMX_LN_COUNT
-            const uint64_t ts0 = __builtin_amdgcn_s_memtime();
             stage(S0, v0, tq0);
-            n_top += (uint32_t)(__builtin_amdgcn_s_memtime() - ts0);  // cycles in stage (slot 9)
-#else
-            stage(S0, v0, tq0);
-#endif
             if (!step() || !step() || !step()) break;
-#ifdef DMX_LN_COUNT
-            const uint64_t ts1 = __builtin_amdgcn_s_memtime();
             stage(S1, v1, tq1);
-            n_top += (uint32_t)(__builtin_amdgcn_s_memtime() - ts1);
-#else
-            stage(S1, v1, tq1);
-#endif
             if (!step() || !step() || !step()) break;
         }
         endbit = bp;
@@ -916,7 +742,7 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
     B.ntok[j] = ntok;
     // 32 KiB segments: a long token list goes on the one-wave resolve's list (the rest: the
     // workgroup resolve, launched over every candidate)
-    if (!SPLIT && kRsSplit && !(r.flags & ~SEGF_FINAL) && ntok > RS_FOLLOW) B.split[2 + atomicAdd(B.split, 1u)] = (uint32_t)j;
+    if (!SPLIT && !(r.flags & ~SEGF_FINAL) && ntok > RS_FOLLOW) B.split[2 + atomicAdd(B.split, 1u)] = (uint32_t)j;
     // the split holds only if the output crossed HALF at a token boundary, or never reached it
     if (SPLIT) B.split[j] = (flags || xhalf || (outpos > HALF && split == ~0u)) ? ~0u : (outpos <= HALF ? ntok : split);
     if (dbg) {  // (slots 5..7 belong to k_inflate_resolve)
@@ -1363,13 +1189,13 @@ __device__ __forceinline__ void ln_resolve_one(const InflateArgs& A, uint64_t j,
 // workgroup whose other waves leave at once still measured 5 % slower on 1 GiB of text).
 template <uint32_t NT>
 __device__ __forceinline__ bool rs_mine(uint32_t n) {
-    return !kRsSplit || ((n <= RS_FOLLOW) == (NT > 64));
+    return (n <= RS_FOLLOW) == (NT > 64);
 }
 template <uint32_t CAP, uint32_t NT>
 __global__ __launch_bounds__(NT) void k_inflate_resolve(InflateArgs A, LaneArgs B) {
     __shared__ __attribute__((aligned(16))) uint8_t win[CAP];  // 32 KiB: five per CU; 64 KiB: two
     const uint64_t j = blockIdx.x;
-    if constexpr (CAP == LN_OUT_CAP && NT == 64 && kRsSplit) {
+    if constexpr (CAP == LN_OUT_CAP && NT == 64) {
         // the long token lists listed by the lanes, drawn by ticket (a grid over every candidate
         // kept a 32 KiB window per empty workgroup: ~15 us on 1 GiB of repeat, which has none)
         // (the first item is the workgroup's own index: no ticket traffic when the list is
@@ -1477,7 +1303,7 @@ hipError_t launch_inflate_lanes(const InflateArgs& A, uint32_t* tok, uint64_t* t
     }
     const bool big = A.slot > LN_OUT_CAP;  // 64 KiB segments (config C4's blocks)
     hipLaunchKernelGGL(k_lane_caps, dim3(g), dim3(256), 0, st, in, A.cands, A.ncand, A.n, caps, heavy, limit, hl,
-                       big ? 2 * LN_OUT_CAP : LN_OUT_CAP, A.ncand_dev, !big && kRsSplit ? split : nullptr);
+                       big ? 2 * LN_OUT_CAP : LN_OUT_CAP, A.ncand_dev, !big ? split : nullptr);
     hipError_t e = launch_scan_u32(caps, tokoff, A.ncand, tokoff + A.ncand, st);
     if (e != hipSuccess) return e;
     LaneArgs B{tok, tokoff, ntok, caps, split};
@@ -1489,18 +1315,14 @@ hipError_t launch_inflate_lanes(const InflateArgs& A, uint32_t* tok, uint64_t* t
         hipLaunchKernelGGL((k_inflate_lanes<2 * LN_OUT_CAP, NL>), lg, dim3(64), 0, st, A, B);
         hipLaunchKernelGGL(k_inflate_resolve_half<RS_NT>, dim3((uint32_t)(2 * A.ncand)), dim3(RS_NT), 0, st, A, B);
         hipLaunchKernelGGL((k_inflate_resolve<2 * LN_OUT_CAP, RS_NT>), dim3((uint32_t)A.ncand), dim3(RS_NT), 0, st, A, B);
-        if (kRsSplit) {
-            hipLaunchKernelGGL(k_inflate_resolve_half<64>, dim3((uint32_t)(2 * A.ncand)), dim3(64), 0, st, A, B);
-            hipLaunchKernelGGL((k_inflate_resolve<2 * LN_OUT_CAP, 64>), dim3((uint32_t)A.ncand), dim3(64), 0, st, A, B);
-        }
+        hipLaunchKernelGGL(k_inflate_resolve_half<64>, dim3((uint32_t)(2 * A.ncand)), dim3(64), 0, st, A, B);
+        hipLaunchKernelGGL((k_inflate_resolve<2 * LN_OUT_CAP, 64>), dim3((uint32_t)A.ncand), dim3(64), 0, st, A, B);
     } else {
         const dim3 lg((uint32_t)((A.ncand + LN_LANES - 1) / LN_LANES));
         hipLaunchKernelGGL((k_inflate_lanes<LN_OUT_CAP, LN_LANES>), lg, dim3(64), 0, st, A, B);
         hipLaunchKernelGGL((k_inflate_resolve<LN_OUT_CAP, RS_NT>), dim3((uint32_t)A.ncand), dim3(RS_NT), 0, st, A, B);
-        if (kRsSplit) {
-            const uint32_t g = (uint32_t)std::min<uint64_t>(A.ncand, (uint64_t)RS_TICKET_WG * (uint64_t)ncu);
-            if (g) hipLaunchKernelGGL((k_inflate_resolve<LN_OUT_CAP, 64>), dim3(g), dim3(64), 0, st, A, B);
-        }
+        const uint32_t g = (uint32_t)std::min<uint64_t>(A.ncand, (uint64_t)RS_TICKET_WG * (uint64_t)ncu);
+        if (g) hipLaunchKernelGGL((k_inflate_resolve<LN_OUT_CAP, 64>), dim3(g), dim3(64), 0, st, A, B);
     }
     if (ev1) (void)hipEventRecord(ev1, st);
     return hipGetLastError();

@@ -308,17 +308,11 @@ FbWalk FbPlan::walk(int round) {
         vmode[Ku] = br.second == FB_AT_HEADER ? FB_V_HEADER : FB_V_EXACT;
         vhdr[Ku] = br.second == FB_AT_HEADER ? 0 : br.second;
         stops[Ku] = stop_of(e);
-        // inside a fixed-code region (after a stored block there, say): the true path's
-        // chunk entries are known, so the repair unit's ranges start exactly on them too
-        // Off (DMX_FB_REPAIR_EXACT, developer A/B): measured Z_FIXED 64 MiB text 4.7 -> 4.2 ms
-        // but 32 MiB mixed 8.7 -> 13.4 ms (a repair unit after a stored block then ends
-        // serially), also with soft stops only.
+        // No exact chunk entries for a repair unit, also inside a fixed-code region where the
+        // true path's are known: starting its ranges on them measured Z_FIXED 64 MiB text
+        // 4.7 -> 4.2 ms but 32 MiB mixed 8.7 -> 13.4 ms (a repair unit after a stored block
+        // then ends serially), also with soft stops only.
         ucb[Ku] = ~0u;
-        if (DMX_FB_REPAIR_EXACT && !regs.empty() && (stops[Ku] & FB_STOP_SOFT)) {
-            auto rg = std::upper_bound(regs.begin(), regs.end(), e, [](uint64_t v, const Reg& g) { return v < g.E; });
-            if (rg != regs.begin() && e < (--rg)->T)
-                ucb[Ku] = (uint32_t)((rg->sb0 + (e - rg->E) / geom.super_bits) * 64);
-        }
         const uint64_t w = (stops[Ku] & FB_STOP_SOFT) ? region_words((stops[Ku] & FB_STOP_MASK) - std::min(e, nbits))
                                                       : std::min(words_of(e, stops[Ku]), kOpenWords);
         if (rep_used + w > rep_words) return {FbWalk::DECLINE, 0, "repair token space", 0, chain.back()};

@@ -66,10 +66,6 @@ SegChain seg_chain_walk(const SegRecord* recs, const uint64_t* cands, uint64_t n
 
 // ---- path 5: the block-parallel decode of arbitrary streams -------------------------------
 
-#ifndef DMX_FB_REPAIR_EXACT
-#define DMX_FB_REPAIR_EXACT 0  // path-5 repair units inside fixed-code regions on exact chunk entries
-#endif
-
 struct FbGeom {  // the region map's geometry (fb_region_*() of inflate_blocks.hip)
     uint64_t super_bits, chunk_bits;
     uint32_t nodes, entries;
@@ -132,7 +128,7 @@ public:
     // ... and write (the driver copies the records of every decoded batch here)
     std::vector<FbUnit> units;
     std::vector<uint8_t> strong;  // scanned units: a dynamic-header start
-    std::vector<Reg> regs;  // (kept for the repair units: exact chunk entries inside a region)
+    std::vector<Reg> regs;  // the fixed-code regions (select_regions)
     uint64_t nsb = 0;       // super blocks of all regions
     // the chain of the last walk
     std::vector<uint32_t> chain;
