@@ -1245,77 +1245,177 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             __syncthreads();
         }
 
-        // ---- token ranges (TokRange): per-word token counts, block scan into the match
-        //      bitmap (dead after the parse), binary search for the thread's first token ------
-        TokRange tr;
-        uint32_t tr_total;  // tokens of the segment
-        {
-            const uint32_t c = t < NMAP ? (uint32_t)__popc(S.tokmap[t]) : 0u;
-            uint32_t tot;
-            const uint32_t ex = block_excl_scan(c, S.scan, &tot);
-            if (t < NMAP) S.mmap[t] = ex;
-            __syncthreads();
-            tr_total = tot;
-            const uint32_t K = (tot + DF_NT - 1) / DF_NT;
-            const uint32_t first = min((uint32_t)t * K, tot);
-            tr.n = min(first + K, tot) - first;
-            uint32_t lo = 0, hi = NMAP;  // largest word lo with pre[lo] <= first
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (S.mmap[mid] <= first) lo = mid;
-                else hi = mid;
-            }
-            tr.w = lo;
-            // drop the word's first r tokens: the r-th set bit by a 5-step popcount search
-            const uint32_t m = S.tokmap[lo];
-            uint32_t b = 0, k = tr.n ? first - S.mmap[lo] : 0u;
-#pragma unroll
-            for (uint32_t sh = 16; sh >= 1; sh >>= 1) {
-                const uint32_t c = (uint32_t)__popc((m >> b) & ((1u << sh) - 1u));
-                const bool up = k >= c;
-                b += up ? sh : 0u;
-                k -= up ? c : 0u;
-            }
-            tr.m = m & (0xFFFFFFFFu << b);
+        // ---- token words of a segment with a terminal run (32 KiB, level 2), by bitmap word:
+        //      thread t owns tokmap[t] and makes the words of its 32 positions, in order --
+        //      literal runs of up to three bytes, closed by a match and at the bitmap word's end,
+        //      one word per match.  Such a segment has a few hundred tokens, fewer than threads,
+        //      so the token ranges below would balance nothing; one block scan of
+        //      (tokens << 16 | words) gives the word offset and both totals (tokens <= 32768,
+        //      words <= 17408: no carry).  k_deflate_emit codes every word on its own, so the
+        //      stream depends on the token sequence only and not on how the literals are grouped
+        //      into words.
+        //      Capacity: a thread's 32 positions make at most one word per two positions plus one
+        //      (a lone literal's word is closed only by a match, of three positions or more; at
+        //      most one match overhangs the bitmap word and one partial literal word ends it):
+        //      17 per thread, 16384 + 1024 = 17408 per segment = tok_stride - 224, so nothing
+        //      writes into the 224 slack words -----
+        bool by_word = false;
+        if constexpr (TERMRUN) {
+            static_assert(NMAP == DF_NT, "one token-start bitmap word per thread");
+            by_word = run_lo != RUN_NONE;
         }
-        DMX_PHASE(A.dbg, seg, 15);
-        // ---- token words for k_deflate_emit, in position order: literal runs of up to three
-        //      bytes per word, one word per match (count, block scan of the counts, write).  A
-        //      segment without a match (every position a token: incompressible data) writes none:
-        //      the emission kernel reads its literals from the input -----
-        const bool all_lit = tr_total == nb - D;
-        if (all_lit) {
-            if (t == 0) A.ntok[seg] = EM_ALL_LITERALS;
-        } else {
-            auto walk = [&](auto emit) {
-                uint32_t w = tr.w, m = tr.m, lit = 0, nl = 0;
-                for (uint32_t i = 0; i < tr.n; i++) {
-                    const uint32_t p = next_tok(S.tokmap, w, m);
-                    const uint32_t d = S.cand[p];
-                    if (d) {
-                        if (nl) emit(lit | (nl << 24));
-                        nl = 0;
-                        lit = 0;
-                        emit(0x80000000u | ((uint32_t)(S.cand[p + 1] - 3) << 16) | (d - 1));
-                    } else {
-                        lit |= (uint32_t)data_byte(data32, p) << (8 * nl);
-                        if (++nl == 3) {
-                            emit(lit | (3u << 24));
-                            nl = 0;
-                            lit = 0;
+        if (by_word) {
+            // The words' first positions by bit operations, not by a walk: a segment's first
+            // occurrence of its period is a few hundred literals in a row, 32 tokens in each of a
+            // few threads, and two token-by-token walks of dependent LDS reads there (one to
+            // count, one to write) took three times as long as the ranges they replaced.
+            // mt: the tokens with a candidate, the matches; lt: the literals.  A literal is one
+            // position long, so the literals between two matches are adjacent bits of lt, and
+            // such a run's words start at its first bit and every third one after it (ws).
+            const uint32_t m = S.tokmap[t];
+            const uint4* const c4 = reinterpret_cast<const uint4*>(S.cand + 32 * t);
+            uint32_t nz = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint4 v = c4[k];
+                const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    nz |= ((x[j] & 0xFFFFu) ? 1u : 0u) << (8 * k + 2 * j);
+                    nz |= ((x[j] >> 16) ? 1u : 0u) << (8 * k + 2 * j + 1);
+                }
+            }
+            const uint32_t mt = m & nz, lt = m & ~nz;
+            const uint32_t chain = lt & (lt << 1) & (lt << 2) & (lt << 3);  // p - 3 .. p are literals
+            uint32_t ws = lt & ~(lt << 1);
+#pragma unroll
+            for (int i = 0; i < 10; i++) ws |= (ws << 3) & chain;
+            // block scan with one barrier: its scratch (the upper entries of S.scan, which
+            // block_excl_scan leaves alone) is next written in a later segment, behind the
+            // segment loop's closing barrier
+            const uint32_t val = ((uint32_t)__popc(m) << 16) | ((uint32_t)__popc(mt) + (uint32_t)__popc(ws));
+            const uint32_t inc = wave_incl_scan(val);
+            uint32_t* const sc = S.scan + DF_NT / 64;
+            if ((t & 63) == 63) sc[t >> 6] = inc;
+            __syncthreads();
+            uint32_t ex = inc - val, tot = 0;
+#pragma unroll
+            for (int i = 0; i < DF_NT / 64; i++) {
+                const uint32_t x = sc[i];
+                if (i < (t >> 6)) ex += x;
+                tot += x;
+            }
+            DMX_PHASE(A.dbg, seg, 15);
+            if ((tot >> 16) == nb - D) {  // (the emission kernel's rule; a run segment has a match)
+                if (t == 0) A.ntok[seg] = EM_ALL_LITERALS;
+            } else {
+                uint32_t* dst = A.tok + seg * (uint64_t)A.tok_stride + (ex & 0xFFFFu);
+                // Four words per step, their LDS reads issued together: two 32-bit words from
+                // the candidates (a match: its distance and, one entry on, its length) or from
+                // the image (one to three literals: the adjacent bits of lt), as word offsets
+                // from the start of S
+                const uint32_t* const sw = reinterpret_cast<const uint32_t*>(&S);
+                const uint32_t cbase = (uint32_t)(reinterpret_cast<const uint32_t*>(S.cand) - sw) + 16 * (uint32_t)t;
+                const uint32_t dbase = (uint32_t)(data32 - sw) + 8 * (uint32_t)t;
+                uint32_t all = mt | ws;
+                while (all) {
+                    uint32_t b[4], lo[4], hi[4];
+                    bool on[4];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        on[i] = all != 0;
+                        b[i] = on[i] ? (uint32_t)__builtin_ctz(all) : 0u;
+                        all &= all - 1;
+                        const uint32_t at = (mt >> b[i]) & 1u ? cbase + (b[i] >> 1) : dbase + (b[i] >> 2);
+                        lo[i] = sw[at];
+                        hi[i] = sw[at + 1];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        if (on[i]) {
+                            const bool mat = (mt >> b[i]) & 1u;
+                            const uint32_t v = __builtin_amdgcn_alignbyte(hi[i], lo[i], mat ? 2 * (b[i] & 1) : b[i] & 3);
+                            const uint32_t x = lt >> b[i], c = 1 + ((x >> 1) & 1u) + ((x >> 1) & (x >> 2) & 1u);
+                            *dst++ = mat ? 0x80000000u | (((v >> 16) - 3) << 16) | ((v & 0xFFFFu) - 1)
+                                         : (v & (0xFFFFFFu >> (24 - 8 * c))) | (c << 24);
                         }
                     }
                 }
-                if (nl) emit(lit | (nl << 24));
-            };
-            uint32_t nw = 0;
-            walk([&](uint32_t) { nw++; });
-            uint32_t wtot;
-            const uint32_t woff = block_excl_scan(nw, S.scan, &wtot);
-            uint32_t* const dst = A.tok + seg * (uint64_t)A.tok_stride + woff;
-            uint32_t j = 0;
-            walk([&](uint32_t v) { dst[j++] = v; });
-            if (t == 0) A.ntok[seg] = wtot;
+                if (t == 0) A.ntok[seg] = tot & 0xFFFFu;
+            }
+        } else {
+            // ---- token ranges (TokRange): per-word token counts, block scan into the match
+            //      bitmap (dead after the parse), binary search for the thread's first token ------
+            TokRange tr;
+            uint32_t tr_total;  // tokens of the segment
+            {
+                const uint32_t c = t < NMAP ? (uint32_t)__popc(S.tokmap[t]) : 0u;
+                uint32_t tot;
+                const uint32_t ex = block_excl_scan(c, S.scan, &tot);
+                if (t < NMAP) S.mmap[t] = ex;
+                __syncthreads();
+                tr_total = tot;
+                const uint32_t K = (tot + DF_NT - 1) / DF_NT;
+                const uint32_t first = min((uint32_t)t * K, tot);
+                tr.n = min(first + K, tot) - first;
+                uint32_t lo = 0, hi = NMAP;  // largest word lo with pre[lo] <= first
+                while (hi - lo > 1) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (S.mmap[mid] <= first) lo = mid;
+                    else hi = mid;
+                }
+                tr.w = lo;
+                // drop the word's first r tokens: the r-th set bit by a 5-step popcount search
+                const uint32_t m = S.tokmap[lo];
+                uint32_t b = 0, k = tr.n ? first - S.mmap[lo] : 0u;
+    #pragma unroll
+                for (uint32_t sh = 16; sh >= 1; sh >>= 1) {
+                    const uint32_t c = (uint32_t)__popc((m >> b) & ((1u << sh) - 1u));
+                    const bool up = k >= c;
+                    b += up ? sh : 0u;
+                    k -= up ? c : 0u;
+                }
+                tr.m = m & (0xFFFFFFFFu << b);
+            }
+            DMX_PHASE(A.dbg, seg, 15);
+            // ---- token words for k_deflate_emit, in position order: literal runs of up to three
+            //      bytes per word, one word per match (count, block scan of the counts, write).  A
+            //      segment without a match (every position a token: incompressible data) writes none:
+            //      the emission kernel reads its literals from the input -----
+            const bool all_lit = tr_total == nb - D;
+            if (all_lit) {
+                if (t == 0) A.ntok[seg] = EM_ALL_LITERALS;
+            } else {
+                auto walk = [&](auto emit) {
+                    uint32_t w = tr.w, m = tr.m, lit = 0, nl = 0;
+                    for (uint32_t i = 0; i < tr.n; i++) {
+                        const uint32_t p = next_tok(S.tokmap, w, m);
+                        const uint32_t d = S.cand[p];
+                        if (d) {
+                            if (nl) emit(lit | (nl << 24));
+                            nl = 0;
+                            lit = 0;
+                            emit(0x80000000u | ((uint32_t)(S.cand[p + 1] - 3) << 16) | (d - 1));
+                        } else {
+                            lit |= (uint32_t)data_byte(data32, p) << (8 * nl);
+                            if (++nl == 3) {
+                                emit(lit | (3u << 24));
+                                nl = 0;
+                                lit = 0;
+                            }
+                        }
+                    }
+                    if (nl) emit(lit | (nl << 24));
+                };
+                uint32_t nw = 0;
+                walk([&](uint32_t) { nw++; });
+                uint32_t wtot;
+                const uint32_t woff = block_excl_scan(nw, S.scan, &wtot);
+                uint32_t* const dst = A.tok + seg * (uint64_t)A.tok_stride + woff;
+                uint32_t j = 0;
+                walk([&](uint32_t v) { dst[j++] = v; });
+                if (t == 0) A.ntok[seg] = wtot;
+            }
         }
         DMX_PHASE(A.dbg, seg, 11);
         // every read of the segment's bytes is done (EARLY: nothing below writes LDS, and the
