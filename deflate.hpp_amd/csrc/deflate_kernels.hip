@@ -457,6 +457,22 @@ struct DfSegAddr {
     const uint8_t* dict;  // the dlen dictionary bytes before it (dlen + nb <= SEG)
     uint32_t dlen;
 };
+// The segments a kernel works on.  A batch built from device-resident descriptors
+// (dmx_deflate_batch_async) keeps the count on the device; A.nseg is then the table's capacity,
+// which the grids are sized for.  Only the batch kernels look: their argument block is a
+// DeflateBatchArgs, which the functions below see through its DeflateArgs base.
+template <bool BATCH>
+__device__ __forceinline__ uint64_t df_nseg(const DeflateArgs& A) {
+    if constexpr (BATCH) {
+        const DeflateBatchArgs& B = static_cast<const DeflateBatchArgs&>(A);
+        if (B.nseg_dev) {
+            const uint64_t d = *B.nseg_dev;
+            return d < A.nseg ? d : A.nseg;
+        }
+    }
+    return A.nseg;
+}
+
 template <int SEG, bool BATCH, bool DICT = false>
 __device__ __forceinline__ DfSegAddr df_seg_addr(const DeflateArgs& A, uint64_t seg) {
     static_assert(!DICT || BATCH, "the dictionary comes with the batch's segment table");
@@ -488,7 +504,7 @@ __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t 
     bool go;
     const uint8_t* nsrc;
     if constexpr (BATCH) {
-        go = seg + gridDim.x < A.nseg;
+        go = seg + gridDim.x < df_nseg<true>(A);
         if (go) {
             const DeflateBatchSeg e = A.btab[seg + gridDim.x];
             nsrc = e.src;
@@ -1448,7 +1464,7 @@ __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SE
         const int t = df_tid();
         if (t < 64) S.buf[t >> 5][SEG / 4 + (t & 31)] = 0;  // (the first segment's barrier covers it)
     }
-    for (uint64_t seg = blockIdx.x; seg < A.nseg; seg += gridDim.x) {
+    for (uint64_t seg = blockIdx.x; seg < df_nseg<BATCH>(A); seg += gridDim.x) {
         deflate_segment<SEG, L3, BATCH, DICT>(A, S, seg, staged, iw);
         // the next segment reuses the LDS (not EARLY: and its prefetch has landed)
         if constexpr (EARLY) {
@@ -1462,15 +1478,29 @@ __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SE
 // instantiations are the single-stream kernels.  DICT: the table's segments may carry a preset
 // dictionary (deflate_segment); 32 KiB segments only -- the 16 KiB kernel has neither the
 // registers nor the image room for it.
+// The batch kernels are templates of their own (k_deflate_segments_batch, ...16_batch): they take
+// a DeflateBatchArgs.  The single-stream templates keep their parameter lists, and so their symbols.
 template <int SEG, bool L3, bool BATCH = false, bool DICT = false>
 __global__ __launch_bounds__(DF_NT) void k_deflate_segments(DeflateArgs A) {
+    static_assert(!BATCH && !DICT, "a batch runs k_deflate_segments_batch");
     __shared__ DfSmem<SEG> S;
-    deflate_segments<SEG, L3, BATCH, DICT>(A, S);
+    deflate_segments<SEG, L3, false, false>(A, S);
 }
 template <bool L3, bool BATCH = false>
 __global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_deflate_segments16(DeflateArgs A) {
+    static_assert(!BATCH, "a batch runs k_deflate_segments16_batch");
     __shared__ DfSmem<16384> S;
-    deflate_segments<16384, L3, BATCH, false>(A, S);
+    deflate_segments<16384, L3, false, false>(A, S);
+}
+template <int SEG, bool L3, bool DICT = false>
+__global__ __launch_bounds__(DF_NT) void k_deflate_segments_batch(DeflateBatchArgs A) {
+    __shared__ DfSmem<SEG> S;
+    deflate_segments<SEG, L3, true, DICT>(A, S);
+}
+template <bool L3>
+__global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_deflate_segments16_batch(DeflateBatchArgs A) {
+    __shared__ DfSmem<16384> S;
+    deflate_segments<16384, L3, true, false>(A, S);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2086,10 +2116,18 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
 // The kernel asks for six waves per SIMD.
 template <int SEG, bool RAW, bool BATCH = false>
 __global__ __launch_bounds__(64 * EM_NW) __attribute__((amdgpu_waves_per_eu(6))) void k_deflate_emit(DeflateArgs A) {
+    static_assert(!BATCH, "a batch runs k_deflate_emit_batch");
     __shared__ EmWave Ws[EM_NW];
     const uint64_t seg = (uint64_t)blockIdx.x * EM_NW + (threadIdx.x >> 6);
     if (seg >= A.nseg) return;
-    em_segment<SEG, RAW, BATCH>(A, Ws[threadIdx.x >> 6], seg);
+    em_segment<SEG, RAW, false>(A, Ws[threadIdx.x >> 6], seg);
+}
+template <int SEG, bool RAW>
+__global__ __launch_bounds__(64 * EM_NW) __attribute__((amdgpu_waves_per_eu(6))) void k_deflate_emit_batch(DeflateBatchArgs A) {
+    __shared__ EmWave Ws[EM_NW];
+    const uint64_t seg = (uint64_t)blockIdx.x * EM_NW + (threadIdx.x >> 6);
+    if (seg >= df_nseg<true>(A)) return;
+    em_segment<SEG, RAW, true>(A, Ws[threadIdx.x >> 6], seg);
 }
 
 // exclusive scan of segment sizes -> offsets (single workgroup of 1024 threads).  Thread t owns
@@ -2232,10 +2270,15 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* slots, uint32_t 
 // (the span of its segments' offsets; A.total holds the end of the last one), DMX_ERR_CAPACITY
 // when that exceeds the capacity -- and, for a buffer without segments (an empty input), the
 // empty final fixed-Huffman block 03 00 that the single-buffer call writes.
-__global__ __launch_bounds__(256) void k_compact_batch(DeflateArgs A) {
+// With a device-side segment count (df_nseg) the split between the two kinds of waves stays at
+// A.nseg, the capacity; the waves between the count and the capacity have no segment.  A buffer
+// marked in A.bflag gets DMX_ERR_ARG, 0 bytes and no output (its segments, if it has any, lie
+// beyond the count).
+__global__ __launch_bounds__(256) void k_compact_batch(DeflateBatchArgs A) {
     const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     if (w < A.nseg) {
+        if (w >= df_nseg<true>(A)) return;
         const uint32_t b = A.btab[w].buf & ~DF_BATCH_LAST;
         const uint32_t sz = A.sizes[w];
         const uint64_t rel = A.offsets[w] - A.offsets[A.bfirst[b]];
@@ -2245,6 +2288,14 @@ __global__ __launch_bounds__(256) void k_compact_batch(DeflateArgs A) {
     }
     const uint64_t b = (w - A.nseg) * 64 + lane;
     if (b >= A.nbuf) return;
+    if (A.bflag && A.bflag[b]) {
+        ::dmx_batch_result r;
+        r.bytes = 0;
+        r.status = DMX_ERR_ARG;
+        r.path = 0;
+        A.bres[b] = r;
+        return;
+    }
     const uint64_t s0 = A.bfirst[b], s1 = A.bfirst[b + 1];
     uint64_t bytes;
     if (s0 == s1) {
@@ -2276,36 +2327,41 @@ uint64_t deflate_front_fit(uint32_t seg_bytes) {
 }
 
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st,
-                          hipEvent_t ev_main0, hipEvent_t ev_main1, bool dict) {
+                          hipEvent_t ev_main0, hipEvent_t ev_main1, bool dict, const uint64_t* nseg_dev,
+                          const uint8_t* bflag) {
     if (dict && (!A.btab || seg_bytes != 32768)) return hipErrorInvalidValue;
     const uint64_t fit = deflate_front_fit(seg_bytes);
     const uint32_t grid = (uint32_t)std::min<uint64_t>(A.nseg, fit);  // host min(int, int) would truncate
     if (ev_main0) (void)hipEventRecord(ev_main0, st);
     if (A.btab) {  // a batch: the same stages over the segment table, k_compact_batch at the end
         if (seg_bytes != 32768 && seg_bytes != 16384) return hipErrorInvalidValue;
+        DeflateBatchArgs B;
+        static_cast<DeflateArgs&>(B) = A;
+        B.nseg_dev = nseg_dev;
+        B.bflag = bflag;
         const bool l3 = A.level >= 3, s32 = seg_bytes == 32768;
         if (grid && A.level >= 2 && dict) {
-            if (l3) hipLaunchKernelGGL((k_deflate_segments<32768, true, true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
-            else hipLaunchKernelGGL((k_deflate_segments<32768, false, true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+            if (l3) hipLaunchKernelGGL((k_deflate_segments_batch<32768, true, true>), dim3(grid), dim3(DF_NT), 0, st, B);
+            else hipLaunchKernelGGL((k_deflate_segments_batch<32768, false, true>), dim3(grid), dim3(DF_NT), 0, st, B);
         } else if (grid && A.level >= 2) {
-            if (s32 && l3) hipLaunchKernelGGL((k_deflate_segments<32768, true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
-            else if (s32) hipLaunchKernelGGL((k_deflate_segments<32768, false, true>), dim3(grid), dim3(DF_NT), 0, st, A);
-            else if (l3) hipLaunchKernelGGL((k_deflate_segments16<true, true>), dim3(grid), dim3(DF_NT), 0, st, A);
-            else hipLaunchKernelGGL((k_deflate_segments16<false, true>), dim3(grid), dim3(DF_NT), 0, st, A);
+            if (s32 && l3) hipLaunchKernelGGL((k_deflate_segments_batch<32768, true>), dim3(grid), dim3(DF_NT), 0, st, B);
+            else if (s32) hipLaunchKernelGGL((k_deflate_segments_batch<32768, false>), dim3(grid), dim3(DF_NT), 0, st, B);
+            else if (l3) hipLaunchKernelGGL((k_deflate_segments16_batch<true>), dim3(grid), dim3(DF_NT), 0, st, B);
+            else hipLaunchKernelGGL((k_deflate_segments16_batch<false>), dim3(grid), dim3(DF_NT), 0, st, B);
         }
         if (A.nseg) {
             const uint32_t eg = (uint32_t)((A.nseg + EM_NW - 1) / EM_NW);
             const bool raw = A.level < 2;
-            if (s32 && raw) hipLaunchKernelGGL((k_deflate_emit<32768, true, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
-            else if (s32) hipLaunchKernelGGL((k_deflate_emit<32768, false, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
-            else if (raw) hipLaunchKernelGGL((k_deflate_emit<16384, true, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
-            else hipLaunchKernelGGL((k_deflate_emit<16384, false, true>), dim3(eg), dim3(64 * EM_NW), 0, st, A);
+            if (s32 && raw) hipLaunchKernelGGL((k_deflate_emit_batch<32768, true>), dim3(eg), dim3(64 * EM_NW), 0, st, B);
+            else if (s32) hipLaunchKernelGGL((k_deflate_emit_batch<32768, false>), dim3(eg), dim3(64 * EM_NW), 0, st, B);
+            else if (raw) hipLaunchKernelGGL((k_deflate_emit_batch<16384, true>), dim3(eg), dim3(64 * EM_NW), 0, st, B);
+            else hipLaunchKernelGGL((k_deflate_emit_batch<16384, false>), dim3(eg), dim3(64 * EM_NW), 0, st, B);
         }
         if (ev_main1) (void)hipEventRecord(ev_main1, st);
         const hipError_t e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st);
         if (e != hipSuccess) return e;
         const uint64_t waves = A.nseg + (A.nbuf + 63) / 64;
-        hipLaunchKernelGGL(k_compact_batch, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(k_compact_batch, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, st, B);
         return hipGetLastError();
     }
     if (grid && A.level >= 2) {  // match finding + parse -> token words (levels 0-1 have none)

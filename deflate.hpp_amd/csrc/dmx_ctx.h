@@ -77,6 +77,7 @@ struct dmx_ctx {
     DevBuf fbJraw, fbJsub, fbcbit, fbucb;  // regions: chunk maps, sub-chunk entries, chunk entries, unit chunk
     DevBuf ck;  // checksum scratch (checksum.hip) + the 4-byte result at its start
     DevBuf btab, bres;  // batch calls: the uploaded tables / descriptors; the results + the ticket
+    DevBuf adf, ainf;   // dmx_*_batch_async: the tables built on the device (deflate; inflate)
     DevBuf fdesc;       // framed batch deflate: {plain input, size, framed output, capacity} per buffer
     // BGZF files in device memory: the deflate's member slots / the ranged read's edge members;
     // the chain scratch (tile counts, candidates, jump tables, member table); descriptors + results

@@ -427,6 +427,124 @@ int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
     return DMX_OK;
 }
 
+// ---- batches from device-resident descriptors (dmx_deflate_batch_async / dmx_inflate_batch_async)
+// The pointer, size and capacity arrays stay on the device: batch_table.hip builds the segment
+// table / the descriptors and the order list there, the batch kernels stop at device-side counts
+// and write the caller's d_res themselves.  The host sizes grids and scratch from count, max_n
+// and max_total alone; once the scratch is large enough a call only enqueues.  The tables live in
+// buffers of their own (c->adf, c->ainf): the synchronous calls' c->btab / c->bres serve both
+// directions and are safe only because those calls end synchronised.
+
+// the deflate's table capacity for a shape (batch_table.h), at least 1
+int async_deflate_capacity(const dmx_ctx* c, size_t count, size_t max_n, size_t max_total, uint32_t du,
+                           uint64_t* cap) {
+    if (bt_segments(max_n, c->seg, du) >= (uint64_t)DF_BATCH_LAST) return DMX_ERR_ARG;  // (a buffer's count is 32 bits)
+    *cap = std::max<uint64_t>(1, bt_capacity(count, max_n, max_total, c->seg, du));
+    return *cap < (uint64_t)DF_BATCH_LAST ? DMX_OK : DMX_ERR_NOMEM;  // (its slots alone would be 64 TiB)
+}
+
+struct AsyncSegTab {  // c->adf: table | bfirst (scan_words(count)) | counts | the segment count | flags
+    DeflateBatchSeg* tab;
+    uint64_t* bfirst;
+    uint32_t* counts;
+    uint64_t* nseg;
+    uint8_t* flag;
+};
+bool async_deflate_scratch(dmx_ctx* c, DeflateArgs& A, AsyncSegTab& T, size_t count, uint64_t cap, int level) {
+    const size_t off_first = cap * sizeof(DeflateBatchSeg), off_counts = off_first + scan_words(count) * 8;
+    const size_t off_nseg = off_counts + (count * 4 + 7) / 8 * 8, off_flag = off_nseg + 8;
+    if (!c->adf.ensure(off_flag + count) || !deflate_scratch(c, A, cap, cap, level, c->seg)) return false;
+    uint8_t* const base = c->adf.as<uint8_t>();
+    T.tab = reinterpret_cast<DeflateBatchSeg*>(base);
+    T.bfirst = reinterpret_cast<uint64_t*>(base + off_first);
+    T.counts = reinterpret_cast<uint32_t*>(base + off_counts);
+    T.nseg = reinterpret_cast<uint64_t*>(base + off_nseg);
+    T.flag = base + off_flag;
+    return true;
+}
+
+int deflate_batch_async_locked(dmx_ctx* c, const uint8_t* const* d_in, const uint64_t* d_n, size_t count,
+                               size_t max_n, size_t max_total, int level, const uint8_t* d_dict, size_t dict_len,
+                               uint8_t* const* d_out, const uint64_t* d_cap, dmx_batch_result* d_res,
+                               hipStream_t st) {
+    if (level < 0 || level > 3) level = 1;  // as deflate_device_locked
+    const uint32_t seg = c->seg;
+    const uint32_t du = level >= 2 ? (uint32_t)std::min<size_t>(dict_len, kDeflateDictMax) : 0u;
+    if (du && seg != 32768) return DMX_ERR_ARG;
+    uint64_t cap = 0;
+    if (const int rc = async_deflate_capacity(c, count, max_n, max_total, du, &cap); rc != DMX_OK) return rc;
+    if (c->df_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_df, 0));
+    DeflateArgs A;
+    AsyncSegTab T;
+    if (!async_deflate_scratch(c, A, T, count, cap, level)) return DMX_ERR_NOMEM;
+    // the sizes past the device-side count stay zero: the scan runs over the capacity
+    HIPCHK(hipMemsetAsync(A.sizes, 0, cap * 4, st));
+    HIPCHK(launch_batch_segtab(d_in, d_n, count, max_n, cap, seg, du, du ? d_dict + (dict_len - du) : nullptr,
+                               T.counts, T.bfirst, T.tab, T.flag, T.nseg, st));
+    A.in = nullptr;
+    A.n = 0;
+    A.final_last = 1;
+    A.total = c->offs.as<uint64_t>() + cap;  // the scan's total follows the offsets (scan_words)
+    A.out = nullptr;
+    A.cap = 0;
+    A.dbg = nullptr;
+    A.btab = T.tab;
+    A.bfirst = T.bfirst;
+    A.bout = d_out;
+    A.bcap = d_cap;
+    A.bres = d_res;
+    A.nbuf = count;
+    HIPCHK(launch_deflate(A, seg, st, nullptr, nullptr, du != 0, T.nseg, T.flag));
+    HIPCHK(hipEventRecord(c->ev_df, st));
+    c->df_pending = true;
+    c->stats = dmx_stats{};
+    c->stats.segments = cap;  // (the table's capacity: the count itself never reaches the host)
+    return DMX_OK;
+}
+
+struct AsyncDescTab {  // c->ainf: descriptors | order | class histogram + cursors | list length | ticket
+    InflateBatchDesc* desc;
+    uint32_t* order;
+    uint32_t* work;
+    uint32_t* norder;
+    unsigned int* ticket;
+};
+bool async_inflate_scratch(dmx_ctx* c, AsyncDescTab& T, size_t count) {
+    const size_t off_order = count * sizeof(InflateBatchDesc), off_work = off_order + (count * 4 + 15) / 16 * 16;
+    const size_t off_norder = off_work + 2 * kBatchClasses * 4, off_ticket = off_norder + 8;
+    if (!c->ainf.ensure(off_ticket + 8)) return false;
+    uint8_t* const base = c->ainf.as<uint8_t>();
+    T.desc = reinterpret_cast<InflateBatchDesc*>(base);
+    T.order = reinterpret_cast<uint32_t*>(base + off_order);
+    T.work = reinterpret_cast<uint32_t*>(base + off_work);
+    T.norder = reinterpret_cast<uint32_t*>(base + off_norder);
+    T.ticket = reinterpret_cast<unsigned int*>(base + off_ticket);
+    return true;
+}
+
+int inflate_batch_async_locked(dmx_ctx* c, const uint8_t* const* d_in, const uint64_t* d_n, size_t count,
+                               size_t max_n, const uint8_t* d_dict, size_t dict_len, uint8_t* const* d_out,
+                               const uint64_t* d_cap, dmx_batch_result* d_res, uint32_t flags, hipStream_t st) {
+    const uint32_t dl = (uint32_t)std::min<size_t>(dict_len, kInflateDictMax);
+    // (the routing rule of inflate_batch_locked; a stream it would route is deferred to the caller)
+    const uint64_t route_bytes = !dl && !(flags & DMX_BATCH_NO_ROUTE) ? kBatchRouteBytes : 0;
+    if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
+    AsyncDescTab T;
+    if (!async_inflate_scratch(c, T, count)) return DMX_ERR_NOMEM;
+    HIPCHK(launch_batch_desc(d_in, d_n, d_out, d_cap, count, max_n, route_bytes, T.desc, T.order, T.norder, T.work,
+                             d_res, st));
+    if (dl)
+        HIPCHK(launch_inflate_batch_dict(T.desc, T.order, count, d_res, T.ticket, c->flags, d_dict + (dict_len - dl), dl,
+                                         st, T.norder));
+    else
+        HIPCHK(launch_inflate_batch(T.desc, T.order, count, d_res, T.ticket, c->flags, st, T.norder));
+    HIPCHK(hipEventRecord(c->ev_inf, st));
+    c->inf_pending = true;
+    c->stats = dmx_stats{};
+    c->stats.segments = count;
+    return DMX_OK;
+}
+
 // Adler-32 / CRC-32 of a device buffer, computed on the GPU (checksum.hip); the value is
 // returned to the host (the call synchronizes the stream).
 int checksum_locked(dmx_ctx* c, bool crc, const uint8_t* d, size_t n, uint32_t init, uint32_t* out,
@@ -761,12 +879,15 @@ void dmx_destroy(dmx_ctx* c) {
     c->subs.clear();
     DeviceGuard dg(c->device);
     (void)hipStreamSynchronize(c->stream);
+    // work enqueued on the callers' streams (the asynchronous calls) still uses the scratch
+    if (c->df_pending && c->ev_df) (void)hipEventSynchronize(c->ev_df);
+    if (c->inf_pending && c->ev_inf) (void)hipEventSynchronize(c->ev_inf);
     for (DevBuf* b : {&c->in, &c->out, &c->slots, &c->sizes, &c->offs, &c->scal, &c->cands,
                       &c->tiles, &c->tileoffs, &c->recs, &c->status, &c->dbg, &c->ltok,
                       &c->ltokoff, &c->lntok, &c->lcaps, &c->lheavy, &c->rtmp, &c->rchain, &c->fbc, &c->fbh, &c->fbo, &c->fbl,
                       &c->fbs, &c->fbt, &c->fbk, &c->fbu, &c->fbch, &c->fbco, &c->fbcs, &c->fbimg, &c->fbstop, &c->fbwin, &c->fbopen, &c->fbvm, &c->fbvh,
                       &c->fbreg, &c->fbJ, &c->fbvis, &c->fbph,
-                      &c->ck, &c->btab, &c->bres, &c->fdesc, &c->bgzs, &c->bgzc, &c->bgzd, &c->bgzt})
+                      &c->ck, &c->btab, &c->bres, &c->adf, &c->ainf, &c->fdesc, &c->bgzs, &c->bgzc, &c->bgzd, &c->bgzt})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -907,6 +1028,67 @@ int dmx_inflate_batch_device(dmx_ctx* c, const void* const* d_in, const size_t* 
                              void* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
                              void* stream) {
     return dmx_inflate_batch_dict_device(c, d_in, n, count, nullptr, 0, d_out, cap, res, flags, stream);
+}
+
+// ---- batches from device-resident descriptor arrays -------------------------------------------
+static bool batch_async_args_ok(const dmx_ctx* c, const void* in, const void* n, size_t count, const void* out,
+                                const void* cap, const void* res) {
+    return c && count < (size_t)DF_BATCH_LAST && (count == 0 || (in && n && out && cap && res));
+}
+
+int dmx_batch_reserve(dmx_ctx* c, size_t count, size_t max_n, size_t max_total, size_t dict_len) {
+    if (!c || count >= (size_t)DF_BATCH_LAST) return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    AsyncDescTab D;
+    if (!async_inflate_scratch(c, D, count)) return DMX_ERR_NOMEM;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_OK;  // no deflate side on 64 KiB contexts
+    // the deflate side at its largest: level 3's token words; a dictionary only where one is taken
+    const uint32_t du = c->seg == 32768 ? (uint32_t)std::min<size_t>(dict_len, kDeflateDictMax) : 0u;
+    uint64_t cap = 0;
+    if (const int rc = async_deflate_capacity(c, count, max_n, max_total, du, &cap); rc != DMX_OK) return rc;
+    if (du) {  // (levels 0-1 ignore the dictionary: their capacity may be the larger one)
+        uint64_t cap0 = 0;
+        if (const int rc = async_deflate_capacity(c, count, max_n, max_total, 0, &cap0); rc != DMX_OK) return rc;
+        cap = std::max(cap, cap0);
+    }
+    DeflateArgs A;
+    AsyncSegTab T;
+    return async_deflate_scratch(c, A, T, count, cap, 3) ? DMX_OK : DMX_ERR_NOMEM;
+}
+
+int dmx_deflate_batch_async(dmx_ctx* c, const void* const* d_in, const uint64_t* d_n, size_t count, size_t max_n,
+                            size_t max_total, int level, const void* d_dict, size_t dict_len, void* const* d_out,
+                            const uint64_t* d_cap, dmx_batch_result* d_res, void* stream) {
+    if (!batch_async_args_ok(c, d_in, d_n, count, d_out, d_cap, d_res) || (dict_len && !d_dict)) return DMX_ERR_ARG;
+    if (c->seg != 16384 && c->seg != 32768) return DMX_ERR_ARG;  // as dmx_deflate_batch_device
+    if (dict_len && c->seg != 32768 && level >= 2 && level <= 3) return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return deflate_batch_async_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), d_n, count, max_n, max_total,
+                                      level, static_cast<const uint8_t*>(d_dict), dict_len,
+                                      reinterpret_cast<uint8_t* const*>(d_out), d_cap, d_res, st);
+}
+
+int dmx_inflate_batch_async(dmx_ctx* c, const void* const* d_in, const uint64_t* d_n, size_t count, size_t max_n,
+                            const void* d_dict, size_t dict_len, void* const* d_out, const uint64_t* d_cap,
+                            dmx_batch_result* d_res, uint32_t flags, void* stream) {
+    if (!batch_async_args_ok(c, d_in, d_n, count, d_out, d_cap, d_res) || (flags & ~DMX_BATCH_NO_ROUTE) ||
+        (dict_len && !d_dict))
+        return DMX_ERR_ARG;
+    if (count == 0) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return inflate_batch_async_locked(c, reinterpret_cast<const uint8_t* const*>(d_in), d_n, count, max_n,
+                                      static_cast<const uint8_t*>(d_dict), dict_len,
+                                      reinterpret_cast<uint8_t* const*>(d_out), d_cap, d_res, flags, st);
 }
 
 // Host buffers: the inputs are packed into one staging image at 16-byte aligned offsets and go up

@@ -6,25 +6,12 @@
 #include "../../include/dmx.h"
 #include "container_parse.h"  // FrameHead, parse_frame (plain C++, shared with the CPU test)
 #include "bgzf_chain.h"       // BgzfCand and the chain steps (plain C++, shared with the CPU test)
+#include "batch_table.h"      // the batch tables' records and build steps (plain C++, shared with the CPU test)
 #include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
 
 namespace dmx {
 
-// One segment of a batch: `nb` bytes at `src`; `tail` bytes are readable from src to the end of
-// its buffer (a word read may not run into a neighbour's allocation).
-// A preset dictionary (dmx_deflate_batch_dict_device): the first segment of every buffer carries
-// the last dlen <= kDeflateDictMax dictionary bytes at dict; the front kernel matches in the image
-// [dictionary bytes | the segment's nb bytes], dlen + nb <= the segment size, and emits tokens
-// for the segment's own bytes only.  dlen == 0: an ordinary segment.
-struct DeflateBatchSeg {
-    const uint8_t* src;
-    uint64_t tail;
-    uint32_t nb;     // <= the context's segment size
-    uint32_t buf;    // buffer index | DF_BATCH_LAST on the last segment of its buffer (BFINAL)
-    const uint8_t* dict;
-    uint64_t dlen;
-};
-constexpr uint32_t DF_BATCH_LAST = 1u << 31;
+// (DeflateBatchSeg, DF_BATCH_LAST and InflateBatchDesc: batch_table.h)
 constexpr uint32_t kDeflateDictMax = 16384;  // dictionary bytes the deflate side uses (the last ones)
 constexpr uint32_t kInflateDictMax = 32768;  // ... and the inflate side: the DEFLATE window
 
@@ -54,6 +41,15 @@ struct DeflateArgs {
     ::dmx_batch_result* bres = nullptr;  // nbuf results, written by k_compact_batch
     uint64_t nbuf = 0;
 };
+// What the batch kernels take (the BATCH instantiations and k_compact_batch): DeflateArgs and,
+// for dmx_deflate_batch_async, the segment count on the device (<= nseg, which is then the
+// table's capacity the grids are sized for; nullptr: nseg is the count) and the buffers that get
+// DMX_ERR_ARG and no output (nullptr: none).  A type of its own: the single-stream kernels'
+// argument block, and with it their code, stays as it is.
+struct DeflateBatchArgs : DeflateArgs {
+    const uint64_t* nseg_dev = nullptr;
+    const uint8_t* bflag = nullptr;
+};
 
 // Token words per segment of the front kernel: a literal word covers 1-3 input bytes, a match
 // word at least 3, so at most seg / 2 words (one literal between every two 3-byte matches), plus
@@ -64,8 +60,11 @@ static_assert(deflate_tok_stride(32768) == 17632 && deflate_tok_stride(16384) ==
               "the token buffers' layout is fixed");
 
 // dict: the batch's segment table carries a preset dictionary (32 KiB segments, levels 2-3)
+// nseg_dev / bflag: a batch's device-side segment count and flagged buffers (DeflateBatchArgs);
+// the caller has zeroed A.sizes[0 .. A.nseg) then
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, hipEvent_t ev0,
-                          hipEvent_t ev1, bool dict = false);
+                          hipEvent_t ev1, bool dict = false, const uint64_t* nseg_dev = nullptr,
+                          const uint8_t* bflag = nullptr);
 // the front kernel's persistent workgroups that fit the GPU at once: workgroup b takes the
 // segments b, b + grid, ... with grid = min(segments, this)
 uint64_t deflate_front_fit(uint32_t seg_bytes);
@@ -241,17 +240,33 @@ hipError_t launch_inflate_serial(const InflateArgs& A, int count_only, InflateRe
 // launch_inflate_batch_dict: dict holds the preset dictionary's last dl bytes, 0 < dl <=
 // kInflateDictMax (device memory, any alignment), which every stream's window holds before its
 // first byte.
-struct InflateBatchDesc {
-    const uint8_t* in;
-    uint64_t n;
-    uint8_t* out;
-    uint64_t cap;
-};
+// norder_dev (dmx_inflate_batch_async): the list's length lives on the device (<= norder, which
+// is then the capacity the grid is sized for); nullptr: norder is the length.
 hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
-                                ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st);
+                                ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st,
+                                const uint32_t* norder_dev = nullptr);
 hipError_t launch_inflate_batch_dict(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
                                      ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags,
-                                     const uint8_t* dict, uint32_t dl, hipStream_t st);
+                                     const uint8_t* dict, uint32_t dl, hipStream_t st,
+                                     const uint32_t* norder_dev = nullptr);
+
+// Batch tables from device-resident descriptor arrays (batch_table.hip; the steps: batch_table.h).
+// launch_batch_segtab: the deflate's segment table for `count` buffers and a capacity of `cap`
+// entries, cap >= 1: counts (count words) and bfirst (scan_words(count) entries) are scratch and
+// the first-segment list; tab holds cap entries, flag count bytes; *nseg = the segments the batch
+// kernels work on.  dtail: the dictionary's last du bytes (du == 0: none).
+hipError_t launch_batch_segtab(const uint8_t* const* in, const uint64_t* n, uint64_t count, uint64_t max_n,
+                               uint64_t cap, uint32_t seg, uint32_t du, const uint8_t* dtail, uint32_t* counts,
+                               uint64_t* bfirst, DeflateBatchSeg* tab, uint8_t* flag, uint64_t* nseg,
+                               hipStream_t st);
+// launch_batch_desc: desc[i] = {in[i], n[i], out[i], cap[i]}; order = the streams the batch kernel
+// keeps, longest class first, *norder of them; a stream above max_n gets DMX_ERR_ARG and one above
+// route_bytes (0: no routing) with an output buffer DMX_BATCH_DEFERRED in res.  work: 2 *
+// kBatchClasses words (the class histogram and the scatter's cursors), zeroed by the launch.
+hipError_t launch_batch_desc(const uint8_t* const* in, const uint64_t* n, uint8_t* const* out, const uint64_t* cap,
+                             uint64_t count, uint64_t max_n, uint64_t route_bytes, InflateBatchDesc* desc,
+                             uint32_t* order, uint32_t* norder, uint32_t* work, ::dmx_batch_result* res,
+                             hipStream_t st);
 
 
 // framed batch calls (checksum.hip, frame_batch.hip; FrameHead and the parse: container_parse.h).

@@ -128,14 +128,21 @@ __device__ __forceinline__ void batch_prefill(uint8_t* ring, const uint8_t* dict
 // this file with DMX_BATCH_DICT set): with both in one unit the decoder's helper functions have
 // two callers, are no longer inlined, and the plain kernel goes from 123 VGPRs and no scratch
 // to 162 VGPRs and 12 bytes of scratch.
+// norder_dev (dmx_inflate_batch_async): the order list's length on the device, at most norder --
+// which is then the capacity the grid was sized for; nullptr: norder is the length.
 template <bool DICT>
 __global__ __launch_bounds__(IF_NT) void k_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order,
                                                          uint64_t norder, ::dmx_batch_result* res,
                                                          unsigned int* ticket, uint32_t flags,
-                                                         const uint8_t* dict, uint32_t dl) {
+                                                         const uint8_t* dict, uint32_t dl,
+                                                         const uint32_t* norder_dev) {
     __shared__ __attribute__((aligned(16))) uint8_t ring[BT_RING];
     __shared__ uint32_t inring[BT_RW];
     __shared__ Tables T;
+    if (norder_dev) {
+        const uint64_t d = *norder_dev;
+        norder = d < norder ? d : norder;
+    }
     for (;;) {
         uint32_t k = 0;
         if (threadIdx.x == 0) k = atomicAdd(ticket, 1u);
@@ -181,11 +188,13 @@ __global__ __launch_bounds__(IF_NT) void k_inflate_batch(const InflateBatchDesc*
 #if DMX_BATCH_DICT
 hipError_t launch_inflate_batch_dict(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
                                      ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags,
-                                     const uint8_t* dict, uint32_t dl, hipStream_t st) {
+                                     const uint8_t* dict, uint32_t dl, hipStream_t st,
+                                     const uint32_t* norder_dev) {
     if (!dict || dl == 0 || dl > kInflateDictMax) return hipErrorInvalidValue;
 #else
 hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* order, uint64_t norder,
-                                ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st) {
+                                ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags, hipStream_t st,
+                                const uint32_t* norder_dev) {
     const uint8_t* const dict = nullptr;
     const uint32_t dl = 0;
 #endif
@@ -200,7 +209,7 @@ hipError_t launch_inflate_batch(const InflateBatchDesc* desc, const uint32_t* or
     const hipError_t e = hipMemsetAsync(ticket, 0, sizeof(unsigned int), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_inflate_batch<DICT>, dim3(grid), dim3(IF_NT), 0, st, desc, order, norder, res, ticket, flags,
-                       dict, dl);
+                       dict, dl, norder_dev);
     return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@ DMX_VERIFY = 1
 DMX_DEFLATE_NOT_FINAL = 1
 DMX_BATCH_NO_ROUTE = 1
 DMX_BATCH_VERIFY = 2
+DMX_BATCH_DEFERRED = 1  # per-buffer status of inflate_batch_async: decode it with inflate_device
 DMX_FRAME_ZLIB = 1
 DMX_FRAME_GZIP = 2
 DMX_FRAME_BGZF = 3
@@ -50,7 +51,7 @@ EXPORTS = [
     "dmx_batch_framed_bound", "dmx_deflate_batch_framed_device", "dmx_inflate_batch_framed_device",
     "dmx_deflate_batch_framed", "dmx_inflate_batch_framed", "dmx_bgzf_bound", "dmx_deflate_bgzf",
     "dmx_inflate_bgzf", "dmx_deflate_bgzf_device", "dmx_bgzf_index_device", "dmx_inflate_bgzf_device",
-    "dmx_inflate_bgzf_range_device",
+    "dmx_inflate_bgzf_range_device", "dmx_batch_reserve", "dmx_deflate_batch_async", "dmx_inflate_batch_async",
 ]
 
 
@@ -155,6 +156,9 @@ def lib():
     L.dmx_inflate_batch_framed_device.argtypes = [vp, vp, vp, sz, u32, vp, vp, brp, u32, vp]
     L.dmx_deflate_batch_framed.argtypes = [vp, vp, vp, sz, ctypes.c_int, u32, vp, vp, brp]
     L.dmx_inflate_batch_framed.argtypes = [vp, vp, vp, sz, u32, vp, vp, brp, u32]
+    L.dmx_batch_reserve.argtypes = [vp, sz, sz, sz, sz]
+    L.dmx_deflate_batch_async.argtypes = [vp, vp, vp, sz, sz, sz, ctypes.c_int, vp, sz, vp, vp, vp, vp]
+    L.dmx_inflate_batch_async.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, u32, vp]
     L.dmx_bgzf_bound.argtypes = [sz]
     L.dmx_bgzf_bound.restype = sz
     L.dmx_deflate_bgzf.argtypes = [vp, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(sz)]
@@ -457,6 +461,36 @@ class Context:
                                                        a_out, a_cap, res, fl, sp), "inflate_batch_dict_device")
         return [(r.bytes, r.status, r.path) for r in res[:k]]
 
+    # ---- asynchronous batches: the descriptor arrays live in device memory -------------------
+    def batch_reserve(self, count, max_n, max_total=0, dict_len=0):
+        """dmx_batch_reserve: grow the scratch for async batches of this shape now (may allocate
+        and synchronise), so that the calls themselves only enqueue."""
+        _check(lib().dmx_batch_reserve(self.h, count, max_n, max_total, dict_len), "batch_reserve")
+
+    def deflate_batch_async(self, d_in, d_n, count, max_n, level, d_out, d_cap, d_res, max_total=0, dict_ptr=None,
+                            dict_len=0, stream=None):
+        """dmx_deflate_batch_async: d_in / d_n / d_out / d_cap are device arrays of `count` 64-bit
+        entries, d_res a device array of count x 16 bytes (batch_results reads it); all raw device
+        pointers.  Enqueues on `stream` and returns: no result is known before the caller
+        synchronises.  max_n bounds every size, max_total their sum (0: unknown)."""
+        _check(lib().dmx_deflate_batch_async(self.h, ctypes.c_void_p(d_in), ctypes.c_void_p(d_n), count, max_n,
+                                             max_total, level, ctypes.c_void_p(dict_ptr) if dict_ptr else None,
+                                             dict_len, ctypes.c_void_p(d_out), ctypes.c_void_p(d_cap),
+                                             ctypes.c_void_p(d_res), ctypes.c_void_p(stream) if stream else None),
+               "deflate_batch_async")
+
+    def inflate_batch_async(self, d_in, d_n, count, max_n, d_out, d_cap, d_res, no_route=False, dict_ptr=None,
+                            dict_len=0, stream=None):
+        """dmx_inflate_batch_async: arrays as in deflate_batch_async.  Without no_route (and without
+        a dictionary) a stream above the routing threshold is not decoded: its status is
+        DMX_BATCH_DEFERRED and the caller decodes it with inflate_device."""
+        _check(lib().dmx_inflate_batch_async(self.h, ctypes.c_void_p(d_in), ctypes.c_void_p(d_n), count, max_n,
+                                             ctypes.c_void_p(dict_ptr) if dict_ptr else None, dict_len,
+                                             ctypes.c_void_p(d_out), ctypes.c_void_p(d_cap), ctypes.c_void_p(d_res),
+                                             DMX_BATCH_NO_ROUTE if no_route else 0,
+                                             ctypes.c_void_p(stream) if stream else None),
+               "inflate_batch_async")
+
     def _batch_host(self, fn, datas, caps, mid=(), tail=()):
         datas = [bytes(d) for d in datas]
         k = len(datas)
@@ -617,6 +651,16 @@ class Context:
 
 
 _default = None
+
+
+def batch_results(tensor):
+    """The d_res array of an async batch call -- a uint8 CUDA tensor of count x 16 bytes -- as
+    [(bytes, status, path)]; the caller has synchronised."""
+    raw = tensor.detach().cpu().contiguous().numpy().tobytes()
+    if len(raw) % ctypes.sizeof(BatchResult):
+        raise ValueError("not a whole number of dmx_batch_result records")
+    res = (BatchResult * (len(raw) // ctypes.sizeof(BatchResult))).from_buffer_copy(raw)
+    return [(r.bytes, r.status, r.path) for r in res]
 
 
 def default_context():

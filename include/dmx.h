@@ -293,6 +293,68 @@ int dmx_inflate_batch_dict(dmx_ctx* ctx, const uint8_t* const* in, const size_t*
                            const uint8_t* dict, size_t dict_len, uint8_t* const* out, const size_t* cap,
                            dmx_batch_result* res, uint32_t flags);
 
+/* ---- asynchronous batches: device-resident descriptors, no host synchronisation -------------
+ * The batch calls above read their pointer / size / capacity arrays on the host and end with a
+ * host synchronisation.  These take the five arrays (d_in, d_n, d_out, d_cap, d_res; `count`
+ * entries each) in DEVICE memory.  The kernels read them when the work runs, not when the call is
+ * made, so they may be written by work queued earlier on `stream` -- a previous kernel's sizes,
+ * the bytes of another call's d_res, a ragged tensor -- and results land in d_res on the device.
+ *
+ * count, max_n, max_total, level, dict_len and flags are host values: they size grids and
+ * scratch.  The call takes the context mutex, enqueues everything on `stream` and returns.  When
+ * the context's scratch is already large enough -- after a dmx_batch_reserve of at least this
+ * shape, or an earlier call of at least this shape -- it makes no host synchronisation, no host
+ * read of device memory and no allocation; otherwise it grows the scratch first (which may
+ * allocate and synchronise), as the synchronous calls do.
+ *
+ * Return value: the call as a whole.  DMX_ERR_ARG: a null context, a null array with count > 0,
+ * count > 2^31 - 1, a 64 KiB context on the deflate side, dict_len > 0 with a null d_dict, a
+ * dictionary at levels 2-3 on a context that is not 32 KiB, an unknown flag, or a max_n beyond
+ * 2^31 segments.  DMX_ERR_NOMEM also when the shape's segment table would pass 2^31 - 1 entries
+ * (give max_total then).  count == 0 is DMX_OK with nothing enqueued.  The pointers in d_in /
+ * d_out are not checked: entry i must be valid for n[i] / cap[i] bytes (the synchronous calls
+ * refuse a null pointer with a non-zero size; these cannot see it).
+ *
+ * Calls on one context are ordered against its other deflate and inflate work, whatever streams
+ * they run on, like dmx_deflate_device_async / dmx_inflate_device_async.  dmx_destroy waits for
+ * enqueued work.  dmx_last_stats after one of these calls reports `segments` only (deflate: the
+ * segment table's capacity; inflate: count) -- the host never learns the byte counts -- and
+ * dmx_set_timing does not apply.  A context with n_gpus > 1 runs the call on its first device.
+ *
+ * Deflate.  max_n bounds every n[i]; max_total bounds their sum (0 = unknown, taken as count *
+ * max_n).  For every buffer with n[i] <= max_n, d_out[i] and d_res[i] are byte for byte what
+ * dmx_deflate_batch_dict_device writes for the same arrays: the same stream, 03 00 for n[i] == 0,
+ * DMX_ERR_CAPACITY with the needed size and nothing written past cap[i].  A buffer with n[i] >
+ * max_n gets status DMX_ERR_ARG, bytes 0, nothing written to d_out[i], and does not disturb its
+ * neighbours.  The segment table holds min(count * K, ceil(max_total / S) + count) entries, S =
+ * the context's segment_bytes, K = the segments of a max_n-byte buffer (first segment S - Du,
+ * later ones S; Du as in the dictionary calls above).  If the actual segments exceed that, the
+ * buffers from the first one that does not fit onward get DMX_ERR_ARG as above, and the buffers
+ * before it are complete and correct.  (With a dictionary a buffer has ceil((n[i] + Du) / S)
+ * segments: a max_total of sum(n[i]) + count * Du always fits.)
+ *
+ * Inflate.  For every stream the batch decoder takes, d_out[i] and d_res[i] equal
+ * dmx_inflate_batch_dict_device(..., DMX_BATCH_NO_ROUTE)'s -- all error codes, DMX_CFG_RFC_STRICT
+ * and path = 6 included.  A stream with n[i] > max_n gets DMX_ERR_ARG.  Without
+ * DMX_BATCH_NO_ROUTE and without a dictionary, a stream above the synchronous call's routing
+ * threshold is not decoded (the single-stream plan it would be routed to is host-driven): its
+ * result is status DMX_BATCH_DEFERRED, bytes 0, path 0, d_out[i] is untouched, and the caller
+ * decodes it with dmx_inflate_device -- the convention of dmx_inflate_device_async's status 1.
+ * With DMX_BATCH_NO_ROUTE, or with a dictionary, every stream stays on the batch decoder.
+ *
+ * Graph capture of these calls has not been tested. */
+#define DMX_BATCH_DEFERRED 1   /* per-buffer status of the async inflate: not decoded here, see above */
+
+/* grow the context's scratch for async batches of this shape (may allocate and synchronise) */
+int dmx_batch_reserve(dmx_ctx* ctx, size_t count, size_t max_n, size_t max_total, size_t dict_len);
+
+int dmx_deflate_batch_async(dmx_ctx* ctx, const void* const* d_in, const uint64_t* d_n, size_t count,
+                            size_t max_n, size_t max_total, int level, const void* d_dict, size_t dict_len,
+                            void* const* d_out, const uint64_t* d_cap, dmx_batch_result* d_res, void* stream);
+int dmx_inflate_batch_async(dmx_ctx* ctx, const void* const* d_in, const uint64_t* d_n, size_t count,
+                            size_t max_n, const void* d_dict, size_t dict_len, void* const* d_out,
+                            const uint64_t* d_cap, dmx_batch_result* d_res, uint32_t flags, void* stream);
+
 /* ---- checksums and containers (not in the reference) -------------------
  * The reference's decompressZlib (inflate.hpp:326-361) skips the 2-byte header and ignores the
  * Adler-32 (SURVEY A-9); inflate.hpp's decompressZlib keeps exactly that.  These entry points

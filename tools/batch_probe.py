@@ -24,11 +24,19 @@ profiles/batch_probe.json, which DESIGN quotes.
    dmx_inflate_bgzf_device (device buffers), alternated in one run, with the chain walk alone
    (dmx_bgzf_index_device) and a 1 MiB ranged read beside them.
 
+6. asynchronous batch calls (--async, writes profiles/batch_probe_async.json): 16384 x 4 KiB and
+   4096 x 64 KiB of text, level 2; dmx_deflate_batch_device / dmx_inflate_batch_device (host
+   descriptor arrays, prebuilt; the call synchronises) against dmx_deflate_batch_async /
+   dmx_inflate_batch_async (device descriptor arrays) plus one torch.cuda.synchronize(),
+   alternated in one run; the async call's host time until it returns; and a deflate -> inflate
+   chain: two synchronous calls with a host read of the sizes between them against two
+   asynchronous calls, one torch op on the stream that takes the sizes, and one synchronise.
+
 Timing: synchronised host wall clock around each call (every call ends in a host
 synchronisation of its own), WARM warm-up repetitions, then REPS measured ones; the median is
 reported with the minimum beside it.
 
-  python tools/batch_probe.py [--reps 20] [--quick] [--dict | --framed [--loop-reps 20] | --bgzf-device]
+  python tools/batch_probe.py [--reps 20] [--quick] [--dict | --framed [--loop-reps 20] | --bgzf-device | --async]
 """
 import argparse
 import ctypes
@@ -348,6 +356,97 @@ def bgzf_device_file(ctx, nbytes, reps):
     return row
 
 
+def async_vs_sync(ctx, count, size, reps):
+    import numpy as np
+    data = dmx.corpus("text", count * size, offset=1 << 20)
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    bound = (dmx.deflate_bound(size) + 15) & ~15
+    d_c = torch.empty(count * bound, dtype=torch.uint8, device="cuda")
+    d_o = torch.empty(count * size, dtype=torch.uint8, device="cuda")
+    ins = [d_in.data_ptr() + i * size for i in range(count)]
+    comps = [d_c.data_ptr() + i * bound for i in range(count)]
+    outs = [d_o.data_ptr() + i * size for i in range(count)]
+    # synchronous side: the host arrays, built once (the calls themselves are what is timed)
+    vp, sz = ctypes.c_void_p * count, ctypes.c_size_t * count
+    h_in, h_comp, h_out = vp(*ins), vp(*comps), vp(*outs)
+    h_size, h_bound, h_clen = sz(*[size] * count), sz(*[bound] * count), sz()
+    h_res = (dmx.BatchResult * count)()
+    res_np = np.frombuffer(h_res, dtype=np.dtype([("bytes", "<u8"), ("status", "<i4"), ("path", "<u4")]))
+    clen_np = np.frombuffer(h_clen, dtype=np.uint64)
+    lib, h = dmx.lib(), ctx.h
+    # asynchronous side: the same arrays as device tensors, the results on the device
+    i64 = lambda v: torch.tensor(v, dtype=torch.int64).cuda()  # noqa: E731
+    t_in, t_comp, t_out = i64(ins), i64(comps), i64(outs)
+    t_size, t_bound = i64([size] * count), i64([bound] * count)
+    t_res = [torch.zeros(count * 16, dtype=torch.uint8, device="cuda") for _ in range(2)]  # deflate, inflate
+    t_clen = torch.zeros(count, dtype=torch.int64, device="cuda")
+    st = torch.cuda.Stream()
+    sp = st.cuda_stream
+    ctx.batch_reserve(count, bound, count * size)
+    host_ms = {"deflate": [], "inflate": []}
+
+    def sizes_to_host():  # the host read of the sizes (the synchronous call has them in h_res)
+        assert (res_np["status"] == dmx.DMX_OK).all()
+        clen_np[:] = res_np["bytes"]
+
+    def df_sync():
+        assert lib.dmx_deflate_batch_device(h, h_in, h_size, count, 2, h_comp, h_bound, h_res, None) == dmx.DMX_OK
+
+    def if_sync():
+        assert lib.dmx_inflate_batch_device(h, h_comp, h_clen, count, h_out, h_size, h_res, 0, None) == dmx.DMX_OK
+
+    def df_async(record=True):
+        t = time.perf_counter()
+        ctx.deflate_batch_async(t_in.data_ptr(), t_size.data_ptr(), count, size, 2, t_comp.data_ptr(),
+                                t_bound.data_ptr(), t_res[0].data_ptr(), max_total=count * size, stream=sp)
+        if record:
+            host_ms["deflate"].append((time.perf_counter() - t) * 1e3)
+
+    def if_async(record=True):
+        t = time.perf_counter()
+        ctx.inflate_batch_async(t_comp.data_ptr(), t_clen.data_ptr(), count, bound, t_out.data_ptr(),
+                                t_size.data_ptr(), t_res[1].data_ptr(), stream=sp)
+        if record:
+            host_ms["inflate"].append((time.perf_counter() - t) * 1e3)
+
+    def take_sizes():
+        with torch.cuda.stream(st):
+            t_clen.copy_(t_res[0].view(torch.int64).view(-1, 2)[:, 0])
+
+    def chain_sync():
+        df_sync()
+        sizes_to_host()
+        if_sync()
+
+    def chain_async():
+        df_async(False)
+        take_sizes()
+        if_async(False)
+
+    ds, da = alternate_all([df_sync, df_async], reps)
+    sizes_to_host()
+    take_sizes()
+    torch.cuda.synchronize()
+    assert (t_clen.cpu().numpy().astype(np.uint64) == clen_np).all(), "async deflate sizes differ"
+    is_, ia = alternate_all([if_sync, if_async], reps)
+    assert d_o.cpu().numpy().tobytes() == data, "round trip mismatch"
+    assert all(r[:2] == (size, dmx.DMX_OK) for r in dmx.batch_results(t_res[1]))
+    d_o.zero_()
+    cs, ca = alternate_all([chain_sync, chain_async], reps)
+    assert d_o.cpu().numpy().tobytes() == data, "chain round trip mismatch"
+    row = {"kind": "text", "count": count, "size": size, "level": 2, "compressed_bytes": int(clen_np.sum()),
+           "deflate_sync": summary(ds), "deflate_async_plus_sync": summary(da),
+           "deflate_async_host_return": summary(host_ms["deflate"][WARM:]),
+           "inflate_sync": summary(is_), "inflate_async_plus_sync": summary(ia),
+           "inflate_async_host_return": summary(host_ms["inflate"][WARM:]),
+           "chain_sync": summary(cs), "chain_async": summary(ca)}
+    m = lambda k: row[k]["median_ms"]  # noqa: E731
+    row["deflate_async_over_sync"] = m("deflate_async_plus_sync") / m("deflate_sync")
+    row["inflate_async_over_sync"] = m("inflate_async_plus_sync") / m("inflate_sync")
+    row["chain_async_over_sync"] = m("chain_async") / m("chain_sync")
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -356,15 +455,34 @@ def main():
     ap.add_argument("--framed", action="store_true", help="only the framed batch and BGZF shapes (part 4)")
     ap.add_argument("--loop-reps", type=int, default=20, help="--framed: repetitions of the single-buffer loops")
     ap.add_argument("--bgzf-device", action="store_true", help="only BGZF in device memory against the host forms (part 5)")
+    ap.add_argument("--async", dest="async_", action="store_true",
+                    help="only the asynchronous batch calls against the synchronous ones (part 6)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     name = ("batch_probe_dict.json" if a.dict else "batch_probe_framed.json" if a.framed else
-            "batch_probe_bgzf.json" if a.bgzf_device else "batch_probe.json")
+            "batch_probe_bgzf.json" if a.bgzf_device else "batch_probe_async.json" if a.async_ else
+            "batch_probe.json")
     a.out = a.out or os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
         sys.exit("batch_probe: no GPU")
     ctx = dmx.Context()
     q = 8 if a.quick else 1
+    if a.async_:
+        result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
+                  "timing": "host wall clock from before the call to after torch.cuda.synchronize(); synchronous "
+                            "and asynchronous forms alternated in one run, Python's garbage collector run between "
+                            "rounds; the synchronous calls go straight to the C ABI with host arrays built once; "
+                            "*_host_return: wall clock of the asynchronous call alone, until it returns",
+                  "async_vs_sync": []}
+        for count, size in ((16384 // q, 4096), (4096 // q, 65536)):
+            row = async_vs_sync(ctx, count, size, a.reps)
+            result["async_vs_sync"].append(row)
+            print(json.dumps(row), flush=True)
+            with open(a.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+        ctx.close()
+        return
     if a.bgzf_device:
         result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": WARM, "quick": a.quick,
                   "timing": "synchronised host wall clock per call, host and device forms alternated in one run, "
