@@ -977,6 +977,11 @@ __global__ __launch_bounds__(FBP_NT) void k_fb_pdecode(FbDecodeArgs A) {
         }
         return k;
     };
+    // status of a range that met "no code" with the token at body bit p, the failing code at
+    // staged bit pa (past p: a distance code): 2 a data error, 3 an over-read (nocode_err)
+    auto bad_st = [&](uint32_t pa, uint32_t tokbit) -> uint32_t {
+        return nocode_err(S.ws * 32 + pa, pa != tokbit ? 16 : 15, end_bytes * 8) == SEGF_OVERREAD ? 3u : 2u;
+    };
     uint32_t dbg_rounds = 0, dbg_attempts = 0;  // DMX_FB_DEBUG (thread 0)
     for (int attempt = 0; attempt < 2 && S.kind == 0; attempt++) {
         dbg_attempts++;
@@ -1040,7 +1045,7 @@ __global__ __launch_bounds__(FBP_NT) void k_fb_pdecode(FbDecodeArgs A) {
                 atomicOr(&S.bmap[p >> 5], 1u << (p & 31));
                 uint32_t a, d;
                 const uint32_t k = tok(win, &pa, &a, &d);
-                if (k == TK_BAD) { st1 = 2; break; }
+                if (k == TK_BAD) { st1 = bad_st(pa, hs + p); break; }
                 p = pa - hs;
                 if (k == TK_EOB) { st1 = 1; break; }
                 if (k == TK_NOP) continue;
@@ -1091,7 +1096,7 @@ __global__ __launch_bounds__(FBP_NT) void k_fb_pdecode(FbDecodeArgs A) {
                     }
                     uint32_t a, d;
                     const uint32_t k = tok(win, &pa, &a, &d);
-                    if (k == TK_BAD) { stn = 2; break; }
+                    if (k == TK_BAD) { stn = bad_st(pa, hs + p); break; }
                     p = pa - hs;
                     if (k == TK_EOB) { stn = 1; break; }
                 }
@@ -1125,7 +1130,7 @@ __global__ __launch_bounds__(FBP_NT) void k_fb_pdecode(FbDecodeArgs A) {
             const uint64_t pe_abs = S.ws * 32 + hs + e;
             if (st != 1 || pe_abs > end_bytes * 8) {
                 S.kind = 3;
-                S.err = st != 1 ? SEGF_ERR_DATA : SEGF_OVERREAD;
+                S.err = st == 2 ? SEGF_ERR_DATA : SEGF_OVERREAD;
                 if (A.stats) atomicAdd(&A.stats[7], 1u);
             }
             S.endbit = pe_abs - base;

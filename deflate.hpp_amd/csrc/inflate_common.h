@@ -266,6 +266,15 @@ __device__ __forceinline__ bool slow_decode(const Meta& m, const Sorted* sorted,
     return false;
 }
 
+// "No code" at stream bit `at`, found in a window that is zero-padded past the stream end;
+// reads: the bits the reference's lookup of that code reads.  The reference looks a code up bit by bit -- up to 15 bits for lit/len,
+// 16 for a distance, 7 for the precode (inflate.hpp:175, 232-242, 251-261) -- so when fewer bits
+// than that remain it runs out of input before it can give up: an over-read, not a data error.
+// (A real prefix that hit would have hit in the padded window too, so none did.)
+__device__ __forceinline__ uint32_t nocode_err(uint64_t at, uint32_t reads, uint64_t end_bits) {
+    return at + reads > end_bits ? SEGF_OVERREAD : SEGF_ERR_DATA;
+}
+
 __device__ void load_fixed(Tables& T) {
     const int lane = lane_id();
     for (int s = lane; s < 288; s += 64) T.llen[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
@@ -460,9 +469,9 @@ __device__ uint32_t fast_header(const Src& src, uint64_t* pos_io, uint64_t end_b
         // errors, in the reference's order per symbol (inflate.hpp:166-206)
         uint32_t lerr = 0;
         if (proc) {
-            if (!e) lerr = SEGF_ERR_DATA;
-            else if (sym == 16 && rfc && idx == 0) lerr = SEGF_ERR_DATA;
+            if (!e) lerr = rp + (uint32_t)lane + 7 > end_rel ? SEGF_OVERREAD : SEGF_ERR_DATA;  // (nocode_err)
             else if (rp + (uint32_t)lane + tl > end_rel) lerr = SEGF_OVERREAD;
+            else if (sym == 16 && rfc && idx == 0) lerr = SEGF_ERR_DATA;
             else if (idx + rep_l > cap && (rfc || val != 0)) lerr = SEGF_ERR_DATA;
         }
         const uint64_t em = __ballot(lerr != 0);
@@ -809,7 +818,8 @@ __device__ uint32_t decode_huffman(BR& br, const Tables& T, Sink& sk, uint64_t s
         uint32_t e = T.llut[v & ((1u << LUT_L) - 1)];
         if (!e) {
             uint32_t sym, len;
-            if (!slow_decode(T.lm, T.lsorted, v & 0x7FFF, LUT_L + 1, &sym, &len)) return SEGF_ERR_DATA;
+            if (!slow_decode(T.lm, T.lsorted, v & 0x7FFF, LUT_L + 1, &sym, &len))
+                return nocode_err(br.abspos(), 15, br.end_bits);
             e = lit_entry(sym, len);
         }
         const uint32_t cl = e & 15, ty = (e >> 4) & 3;
@@ -830,7 +840,8 @@ __device__ uint32_t decode_huffman(BR& br, const Tables& T, Sink& sk, uint64_t s
         uint32_t de = T.dlut[v & ((1u << LUT_D) - 1)];
         if (!de) {
             uint32_t ds, dl;
-            if (!slow_decode(T.dm, T.dsorted, v & 0x7FFF, LUT_D + 1, &ds, &dl)) return SEGF_ERR_DATA;
+            if (!slow_decode(T.dm, T.dsorted, v & 0x7FFF, LUT_D + 1, &ds, &dl))
+                return nocode_err(br.abspos(), 16, br.end_bits);
             de = dist_entry(ds, dl);
         }
         const uint32_t dl = de & 15, dx = (de >> 6) & 15;

@@ -1213,14 +1213,15 @@ __device__ __attribute__((noinline)) SkState sk_loop(GlbU32* w, uint64_t nwords,
         flag[lane] = 0;
         flag[64 + lane] = 0;
         // a token that ends the block: the last chain member, if its kind says so
-        uint32_t stopk = SK_LIT;
+        uint32_t stopk = SK_LIT, stopl = 0;
         {
             const uint32_t last = Mb ? 127u - (uint32_t)__clzll(Mb) : 63u - (uint32_t)__clzll(Ma);
             const uint32_t t = last < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ia, (int)last)
                                          : (uint32_t)__builtin_amdgcn_readlane((int)ib, (int)(last - 64));
             if ((t >> 8) >= SK_EOB) {
                 stopk = t >> 8;
-                q = last + (t & 255);
+                stopl = t & 255;
+                q = last + stopl;
             }
         }
         stamp(1);
@@ -1302,8 +1303,8 @@ __device__ __attribute__((noinline)) SkState sk_loop(GlbU32* w, uint64_t nwords,
         if (pos - flushed >= 32768) flush();
         cy[5]++;
         p += q;
-        if (stopk == SK_BAD) {
-            S.err = SEGF_ERR_DATA;
+        if (stopk == SK_BAD) {  // p: the code nothing matched (stopl: a distance code, behind a length)
+            S.err = nocode_err(p, stopl ? 16 : 15, endb);
             break;
         }
         if (stopk == SK_EOB) {
@@ -1941,8 +1942,8 @@ __device__ __attribute__((noinline)) void sw_block(SwSmem& S, GlbU32* w, uint64_
             nextp += v + (e & 63);
             if (kind == SK_EOB) {
                 done = true;
-            } else if (kind == SK_BAD) {
-                err = SEGF_ERR_DATA;
+            } else if (kind == SK_BAD) {  // nextp: the code nothing matched
+                err = nocode_err(nextp, (e & 63) ? 16 : 15, endb);
                 done = true;
             }
         }

@@ -10,6 +10,8 @@ Outputs (all data, no reference source):
   expect/*.bin        expected inflate outputs kept in full (small / lossy cases)
   manifest.json       per stream: input file, expected output sha256 + size or the
                       reference's error, and how the vector was produced
+  lenient_manifest.json  (--lenient) digests of the seeded streams of tests/lenient_streams.py
+                      and of the reference's outputs for them
 """
 import hashlib
 import json
@@ -207,8 +209,31 @@ def quirk_manifest(ref, man):
                                  "sync flush, quirk section Q1..Q5, preset-dictionary second half)"}
 
 
+def lenient_manifest(ref):
+    """12. the seeded lenient / edge-case streams of tests/lenient_streams.py: per family the
+    digest of the streams and the digest over the reference's (length, SHA-256) records of the
+    cases the oracle decodes (on the others the reference is undefined and is not called).
+    Data only; written to lenient_manifest.json."""
+    import lenient_streams as LS
+    from oracle_bind import Oracle
+    orc = Oracle()
+    man = {"generator": "tests/lenient_streams.py", "cases_per_family": LS.N_CASES, "families": {}}
+    for fam in LS.FAMILIES:
+        outs = [ref.decompress(c.stream) if LS.expected(orc, c.stream)[1] is None else None
+                for c in LS.cases(fam)]
+        man["families"][fam] = {"streams_sha256": LS.streams_digest(fam),
+                                "decoded": sum(o is not None for o in outs),
+                                "reference_records_sha256": LS.records_digest(outs)}
+    return man
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["--quirks"]:  # only (re)write the quirk entry of the existing manifest
+    if sys.argv[1:] == ["--lenient"]:  # only (re)write lenient_manifest.json
+        m = lenient_manifest(Reference())
+        with open(os.path.join(HERE, "lenient_manifest.json"), "w") as f:
+            json.dump(m, f, indent=1)
+        print(m)
+    elif sys.argv[1:] == ["--quirks"]:  # only (re)write the quirk entry of the existing manifest
         mp = os.path.join(HERE, "manifest.json")
         m = json.load(open(mp))
         quirk_manifest(Reference(), m)
