@@ -499,8 +499,10 @@ __device__ __forceinline__ DfSegAddr df_seg_addr(const DeflateArgs& A, uint64_t 
     return s;
 }
 
-template <int SEG, bool BATCH, bool DICT = false>
+// PIPE (one chunk of the chunk pipeline, DeflatePipeArgs): the look-ahead stops at the chunk's end.
+template <int SEG, bool BATCH, bool DICT = false, bool PIPE = false>
 __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t seg, uint32_t* image) {
+    static_assert(!PIPE || !BATCH, "the chunk pipeline is the single-stream path's");
     bool go;
     const uint8_t* nsrc;
     if constexpr (BATCH) {
@@ -517,7 +519,9 @@ __device__ __forceinline__ bool df_prefetch_next(const DeflateArgs& A, uint64_t 
     } else {
         const uint64_t nbase = (seg + gridDim.x) * (uint64_t)SEG;
         nsrc = A.in + nbase;
-        go = seg + gridDim.x < A.nseg && nbase + SEG <= A.n && ((reinterpret_cast<uintptr_t>(A.in + nbase) & 15) == 0);
+        uint64_t end = A.nseg;
+        if constexpr (PIPE) end = static_cast<const DeflatePipeArgs&>(A).seg_end;
+        go = seg + gridDim.x < end && nbase + SEG <= A.n && ((reinterpret_cast<uintptr_t>(A.in + nbase) & 15) == 0);
     }
     if (go) {
         const int t = df_tid();
@@ -593,7 +597,7 @@ __device__ __forceinline__ void df_load_at(uint8_t* dbytes, uint32_t off, const 
 // bytes are the last of the dictionary, which the decoder's window holds just before the
 // stream's first byte.  Below, nb is the image's length and D the first position with a token;
 // without DICT (and for the later segments of a buffer) D = 0 and nb = the segment's bytes.
-template <int SEG, bool L3, bool BATCH, bool DICT>
+template <int SEG, bool L3, bool BATCH, bool DICT, bool PIPE = false>
 __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG>& S, uint64_t seg,
                                                 uint32_t& staged, [[maybe_unused]] uint32_t iw) {
     constexpr bool EARLY = DfSmem<SEG>::EARLY;
@@ -1013,7 +1017,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         DMX_PHASE(A.dbg, seg, 2);
         // Early load: the table is dead (every wave has passed its last read of it), so the next
         // segment's bytes travel into it during the walk; the barrier after the walk waits for them
-        if constexpr (EARLY) staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, U);
+        if constexpr (EARLY) staged = df_prefetch_next<SEG, BATCH, DICT, PIPE>(A, seg, U);
 
         // ---- parse walk: one DF_CHUNK-byte chunk per quad of lanes (the four walk in step and
         //      share the match-length compares, matchlen4); jumps over literal runs with the
@@ -1438,7 +1442,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // loop's closing barrier stands for this one)
         if constexpr (!EARLY) {
             __syncthreads();
-            staged = df_prefetch_next<SEG, BATCH, DICT>(A, seg, data32);
+            staged = df_prefetch_next<SEG, BATCH, DICT, PIPE>(A, seg, data32);
         }
         DMX_PHASE(A.dbg, seg, 10);
     }
@@ -1455,7 +1459,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
 // staged (an unaligned source, a short or a dictionary segment) loads into its image buffer at
 // its start.  The 128 bytes after each buffer's first SEG are zeroed once: the table never
 // writes there and a staged load brings exactly SEG bytes.
-template <int SEG, bool L3, bool BATCH, bool DICT>
+template <int SEG, bool L3, bool BATCH, bool DICT, bool PIPE = false>
 __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SEG>& S) {
     constexpr bool EARLY = DfSmem<SEG>::EARLY;
     uint32_t staged = 0;  // the image already holds the segment's bytes
@@ -1464,8 +1468,15 @@ __device__ __forceinline__ void deflate_segments(const DeflateArgs& A, DfSmem<SE
         const int t = df_tid();
         if (t < 64) S.buf[t >> 5][SEG / 4 + (t & 31)] = 0;  // (the first segment's barrier covers it)
     }
-    for (uint64_t seg = blockIdx.x; seg < df_nseg<BATCH>(A); seg += gridDim.x) {
-        deflate_segment<SEG, L3, BATCH, DICT>(A, S, seg, staged, iw);
+    uint64_t first = 0;
+    if constexpr (PIPE) first = static_cast<const DeflatePipeArgs&>(A).seg_first;
+    // (a batch's device-side count is read again for every segment, as before the pipeline)
+    const auto end = [&]() -> uint64_t {
+        if constexpr (PIPE) return static_cast<const DeflatePipeArgs&>(A).seg_end;
+        else return df_nseg<BATCH>(A);
+    };
+    for (uint64_t seg = first + blockIdx.x; seg < end(); seg += gridDim.x) {
+        deflate_segment<SEG, L3, BATCH, DICT, PIPE>(A, S, seg, staged, iw);
         // the next segment reuses the LDS (not EARLY: and its prefetch has landed)
         if constexpr (EARLY) {
             df_lds_barrier();
@@ -1501,6 +1512,16 @@ template <bool L3>
 __global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_deflate_segments16_batch(DeflateBatchArgs A) {
     __shared__ DfSmem<16384> S;
     deflate_segments<16384, L3, true, false>(A, S);
+}
+// One chunk of the chunk pipeline (launch_deflate): the segments [A.seg_first, A.seg_end) on a
+// persistent grid, capped at 104 registers so that one emission wave of 80 fits each SIMD beside
+// the workgroup's four (4 x 104 + 80 <= 512).  amdgpu_num_vgpr counts half of the unified
+// register file on gfx90a and later: the compiler doubles the figure, and drops a request whose
+// double lies outside the range of the kernel's occupancy (4 waves per SIMD: 97..128).
+template <bool L3>
+__global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_num_vgpr(52))) void k_deflate_segments_pipe(DeflatePipeArgs A) {
+    __shared__ DfSmem<32768> S;
+    deflate_segments<32768, L3, false, false, true>(A, S);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1542,6 +1563,7 @@ struct EmWave {
     uint32_t start[2][16];   // per alphabet: first rank of code length l
     uint32_t next[2][16];    // per alphabet: first canonical code of length l
 };
+static_assert(3 * sizeof(EmWave) <= 163840 - 140320, "three emission waves fit beside a front workgroup's LDS");
 
 struct EmCodes {
     uint32_t dyn_tok, fix_tok;  // token bits under the dynamic / the fixed code (EOB included)
@@ -2122,6 +2144,16 @@ __global__ __launch_bounds__(64 * EM_NW) __attribute__((amdgpu_waves_per_eu(6)))
     if (seg >= A.nseg) return;
     em_segment<SEG, RAW, false>(A, Ws[threadIdx.x >> 6], seg);
 }
+// One chunk of the chunk pipeline: the segments [A.seg_first, A.seg_end), NW waves per workgroup.
+// NW = 1 beside a resident front workgroup, whose 140,320 bytes of LDS leave room for three
+// one-wave workgroups (6,008 bytes each) and for no four-wave one.
+template <int SEG, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(6))) void k_deflate_emit_pipe(DeflatePipeArgs A) {
+    __shared__ EmWave Ws[NW];
+    const uint64_t seg = A.seg_first + (uint64_t)blockIdx.x * NW + (threadIdx.x >> 6);
+    if (seg >= A.seg_end) return;
+    em_segment<SEG, false, false>(A, Ws[threadIdx.x >> 6], seg);
+}
 template <int SEG, bool RAW>
 __global__ __launch_bounds__(64 * EM_NW) __attribute__((amdgpu_waves_per_eu(6))) void k_deflate_emit_batch(DeflateBatchArgs A) {
     __shared__ EmWave Ws[EM_NW];
@@ -2326,13 +2358,70 @@ uint64_t deflate_front_fit(uint32_t seg_bytes) {
     return (uint64_t)max(ncu, 1) * (uint64_t)max(per, 1);
 }
 
+// The chunk pipeline: chunk i's front kernel on the caller's stream, its emission on the side
+// stream behind an event, so that it runs beside chunk i + 1's front kernel (whose workgroups
+// leave every SIMD 96 registers and every CU 23,520 bytes of LDS: one emission wave per SIMD,
+// three per CU).  Events are the only ordering; the caller's stream continues (scan, k_compact)
+// behind the side stream's last emission.  An emission reads the input itself (stored and all-literal blocks):
+// it is ordered behind the caller's earlier work through its chunk's event.
+static hipError_t launch_deflate_pipe(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, const DeflatePipe& P) {
+    const uint32_t halves = seg_bytes == 65536 ? 2 : 1;
+    const uint64_t nfront = seg_bytes == 65536 ? (A.n + 32767) / 32768 : A.nseg;
+    const uint64_t fit = deflate_front_fit(32768);
+    const uint64_t nchunk = pipe_chunk_count(A.nseg, P.chunk);
+    DeflatePipeArgs F, E;
+    static_cast<DeflateArgs&>(F) = A;
+    static_cast<DeflateArgs&>(E) = A;
+    F.nseg = nfront;  // (64 KiB blocks: the front kernel counts halves)
+    F.dbg = nullptr;
+    for (uint64_t i = 0; i < nchunk; i++) {
+        const PipeRange r = pipe_range(A.nseg, P.chunk, i), f = pipe_front_range(r, halves, nfront);
+        F.seg_first = f.first, F.seg_end = f.end;
+        E.seg_first = r.first, E.seg_end = r.end;
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(f.end - f.first, fit);
+        if (grid) {
+            if (A.level >= 3) hipLaunchKernelGGL(k_deflate_segments_pipe<true>, dim3(grid), dim3(DF_NT), 0, st, F);
+            else hipLaunchKernelGGL(k_deflate_segments_pipe<false>, dim3(grid), dim3(DF_NT), 0, st, F);
+        }
+        // The last chunk has no front kernel to run beside: its emission follows its front kernel
+        // on the caller's stream, without waiting for the side stream's emission before it.
+        const bool last = i + 1 == nchunk;
+        if (!last) {
+            hipError_t e = hipEventRecord(P.ev_chunk, st);
+            if (e == hipSuccess) e = hipStreamWaitEvent(P.side, P.ev_chunk, 0);
+            if (e != hipSuccess) return e;
+        }
+        const hipStream_t es = last ? st : P.side;
+        const uint64_t ne = r.end - r.first;
+        // one-wave workgroups (the last chunk's too: the four-wave form of this kernel spills a
+        // register more than k_deflate_emit)
+        if (halves == 2) hipLaunchKernelGGL((k_deflate_emit_pipe<65536, 1>), dim3((uint32_t)ne), dim3(64), 0, es, E);
+        else hipLaunchKernelGGL((k_deflate_emit_pipe<32768, 1>), dim3((uint32_t)ne), dim3(64), 0, es, E);
+    }
+    hipError_t e = hipEventRecord(P.ev_side, P.side);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, P.ev_side, 0);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st,
                           hipEvent_t ev_main0, hipEvent_t ev_main1, bool dict, const uint64_t* nseg_dev,
-                          const uint8_t* bflag) {
+                          const uint8_t* bflag, const DeflatePipe* pipe) {
     if (dict && (!A.btab || seg_bytes != 32768)) return hipErrorInvalidValue;
+    if (pipe && (A.btab || A.level < 2 || seg_bytes < 32768 || A.dbg || !pipe->chunk || pipe->chunk >= A.nseg))
+        return hipErrorInvalidValue;
     const uint64_t fit = deflate_front_fit(seg_bytes);
     const uint32_t grid = (uint32_t)std::min<uint64_t>(A.nseg, fit);  // host min(int, int) would truncate
     if (ev_main0) (void)hipEventRecord(ev_main0, st);
+    if (pipe) {
+        hipError_t e = launch_deflate_pipe(A, seg_bytes, st, *pipe);
+        if (e != hipSuccess) return e;
+        if (ev_main1) (void)hipEventRecord(ev_main1, st);
+        e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_compact, dim3((uint32_t)((A.nseg + 3) / 4)), dim3(256), 0, st, A.slots, A.slot_bytes,
+                           A.sizes, A.offsets, A.nseg, A.out, A.cap);
+        return hipGetLastError();
+    }
     if (A.btab) {  // a batch: the same stages over the segment table, k_compact_batch at the end
         if (seg_bytes != 32768 && seg_bytes != 16384) return hipErrorInvalidValue;
         DeflateBatchArgs B;

@@ -89,6 +89,11 @@ struct dmx_ctx {
     hipEvent_t ev_inf = nullptr;         // end of the last asynchronous inflate's work
     bool inf_pending = false;
     bool df_pending = false;
+    // the deflate's chunk pipeline: the knob (DMX_DEFLATE_PIPE, read at dmx_create) and, from the
+    // first call that takes it, the side stream of the emission kernels and its two events
+    dmx::PipeKnob pipe{};
+    hipStream_t side = nullptr;
+    hipEvent_t ev_chunk = nullptr, ev_side = nullptr;
     dmx_stats stats{};
     uint64_t last_end = 0;               // the last inflate: stream byte just past its final block
     std::vector<dmx_ctx*> subs;          // n_gpus > 1: one context per shard / piece
@@ -102,6 +107,8 @@ namespace dmx {
 //   DMX_FB_DEBUG=1    block-parallel path: unit outcomes and chain breaks on stderr
 //   DMX_FB_HOSTTIME=1 block-parallel path: host wall clock per phase on stderr
 //   DMX_RECS=1        segmented inflate: per-candidate outcome of each pass on stderr
+// A developer switch of its own, read at every dmx_create (deflate_pipe.h: pipe_knob):
+//   DMX_DEFLATE_PIPE=0|1|<chunks>|s<segments>  the deflate's chunk pipeline
 enum : uint32_t { DIAG_PHASES = 1, DIAG_FB = 2, DIAG_RECS = 4, DIAG_DEBUG = 8, DIAG_FBT = 16 };
 struct Diag {
     uint32_t bits = 0;

@@ -7,6 +7,7 @@
 #include "container_parse.h"  // FrameHead, parse_frame (plain C++, shared with the CPU test)
 #include "bgzf_chain.h"       // BgzfCand and the chain steps (plain C++, shared with the CPU test)
 #include "batch_table.h"      // the batch tables' records and build steps (plain C++, shared with the CPU test)
+#include "deflate_pipe.h"     // the chunk pipeline's chunk arithmetic (plain C++, shared with the CPU test)
 #include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
 
 namespace dmx {
@@ -50,6 +51,20 @@ struct DeflateBatchArgs : DeflateArgs {
     const uint64_t* nseg_dev = nullptr;
     const uint8_t* bflag = nullptr;
 };
+// What the chunk pipeline's kernels take: DeflateArgs and the chunk's segment range (front
+// segments for the front kernel, emission segments for the emission kernel).  nseg stays the
+// call's segment count: the last segment of the stream is still seg + 1 == nseg.
+struct DeflatePipeArgs : DeflateArgs {
+    uint64_t seg_first = 0, seg_end = 0;
+};
+// The chunk pipeline of one call (deflate_pipe.h): chunks of `chunk` segments, the front kernel
+// on the caller's stream, each chunk's emission on `side` behind `ev_chunk` (the last chunk's on
+// the caller's stream), and the caller's stream behind the side stream's emissions through `ev_side`.
+struct DeflatePipe {
+    uint64_t chunk;
+    hipStream_t side;
+    hipEvent_t ev_chunk, ev_side;
+};
 
 // Token words per segment of the front kernel: a literal word covers 1-3 input bytes, a match
 // word at least 3, so at most seg / 2 words (one literal between every two 3-byte matches), plus
@@ -62,9 +77,10 @@ static_assert(deflate_tok_stride(32768) == 17632 && deflate_tok_stride(16384) ==
 // dict: the batch's segment table carries a preset dictionary (32 KiB segments, levels 2-3)
 // nseg_dev / bflag: a batch's device-side segment count and flagged buffers (DeflateBatchArgs);
 // the caller has zeroed A.sizes[0 .. A.nseg) then
+// pipe: the chunk pipeline (single stream, levels 2-3, 32 or 64 KiB segments, no DMX_PHASES)
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, hipEvent_t ev0,
                           hipEvent_t ev1, bool dict = false, const uint64_t* nseg_dev = nullptr,
-                          const uint8_t* bflag = nullptr);
+                          const uint8_t* bflag = nullptr, const DeflatePipe* pipe = nullptr);
 // the front kernel's persistent workgroups that fit the GPU at once: workgroup b takes the
 // segments b, b + grid, ... with grid = min(segments, this)
 uint64_t deflate_front_fit(uint32_t seg_bytes);

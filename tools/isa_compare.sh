@@ -10,7 +10,7 @@
 # instead: the body from the function's label to its .Lfunc_end, for every function of either
 # side whose name matches -- for a file that differs as a whole because other kernels in it
 # changed.  The numbers the assembler gives a function by its position in the file (.LBB<k>_,
-# .Lfunc_end<k>) are replaced by fixed words.
+# .Lfunc_end<k>, and the BB<k>_ of the loop comments) are replaced by fixed words.
 set -eu
 [ $# -eq 1 ] || [ $# -eq 2 ] || { echo "usage: $0 <git-rev> [kernel-regex]" >&2; exit 2; }
 filter=${2:-}
@@ -34,7 +34,7 @@ done | xargs -P 16 -L 1 sh -c "$HIPCC $flags --cuda-device-only -S \"\$0\" -o \"
 # the body of function $2 in assembly file $1, position-dependent label numbers removed
 body() {
     awk -v f="$2:" 'index($0, f) == 1 { on = 1 } on { print } on && /^\.Lfunc_end[0-9]+:/ { exit }' "$1" |
-        sed -E 's/\.LBB[0-9]+_/.LBB_/g; s/\.Lfunc_end[0-9]+/.Lfunc_end/g; s/__hip_cuid_[0-9a-f]+/__hip_cuid_X/g'
+        sed -E 's/\.LBB[0-9]+_/.LBB_/g; s/(Header=|Loop )BB[0-9]+_/\1BB_/g; s/^(\.LBB_[0-9]+:)[[:space:]]+;/\1 ;/; s/\.Lfunc_end[0-9]+/.Lfunc_end/g; s/__hip_cuid_[0-9a-f]+/__hip_cuid_X/g'
 }
 
 rc=0
