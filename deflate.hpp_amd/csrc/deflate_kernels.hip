@@ -2172,6 +2172,9 @@ __global__ __launch_bounds__(64 * EM_NW) __attribute__((amdgpu_waves_per_eu(6)))
 // from the sum of the blocks before it.  (Round 4 scanned with one 1024-thread workgroup: ~20 us
 // for the 32768 segment sizes of 1 GiB, the bandwidth of one CU.)
 constexpr uint32_t SCAN_NT = 256, SCAN_PER = 32, SCAN_BLK = SCAN_NT * SCAN_PER;
+// up to this many blocks k_scan_apply sums the earlier blocks' values itself (at most 7 x 32 more
+// loads per thread) and k_scan_part is not launched: the 32768 sizes of 1 GiB are four blocks
+constexpr uint32_t SCAN_ONE = 8;
 __device__ __forceinline__ void scan_load32(const uint32_t* v, uint64_t i, uint64_t n, bool vec, uint32_t (&x)[32]) {
     if (vec && i + 32 <= n) {
         const uint4* s4 = reinterpret_cast<const uint4*>(v + i);
@@ -2223,14 +2226,28 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_part(const uint32_t* v, uint64
     (void)scan_block64(s, part, &all);
     if (threadIdx.x == 0) partial[blockIdx.x] = all;
 }
+// (total_host: the context's host-mapped result word for the same total; count_dev: a device
+// word that receives total + 1, the candidate count of a marker scan; each or nullptr)
 __global__ __launch_bounds__(SCAN_NT) void k_scan_apply(const uint32_t* v, uint64_t n, const uint64_t* partial,
-                                                        uint64_t* offs, uint64_t* total) {
+                                                        uint64_t* offs, uint64_t* total, uint64_t* total_host,
+                                                        uint64_t* count_dev) {
     __shared__ uint64_t part[SCAN_NT / 64];
     __shared__ uint64_t base_s;
     const int t = threadIdx.x;
-    // the blocks before this one
+    // the blocks before this one: their sums from k_scan_part, or (partial == nullptr, at most
+    // SCAN_ONE blocks) their values themselves, 32 per thread and block
     uint64_t pb = 0;
-    for (uint32_t b = t; b < blockIdx.x; b += SCAN_NT) pb += partial[b];
+    if (partial) {
+        for (uint32_t b = t; b < blockIdx.x; b += SCAN_NT) pb += partial[b];
+    } else {
+        const bool vecv = (reinterpret_cast<uintptr_t>(v) & 15) == 0;
+        for (uint32_t b = 0; b < blockIdx.x; b++) {
+            uint32_t y[32];
+            scan_load32(v, (uint64_t)b * SCAN_BLK + (uint64_t)t * SCAN_PER, n, vecv, y);
+#pragma unroll
+            for (int k = 0; k < 32; k++) pb += y[k];
+        }
+    }
     uint64_t bsum;
     (void)scan_block64(pb, part, &bsum);
     if (t == 0) base_s = bsum;
@@ -2260,7 +2277,11 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_apply(const uint32_t* v, uint6
         for (int k = 0; k < 32; k++)
             if (i + k < n) offs[i + k] = o[k];
     }
-    if (blockIdx.x == gridDim.x - 1 && t == 0) *total = base + all;
+    if (blockIdx.x == gridDim.x - 1 && t == 0) {
+        *total = base + all;
+        if (total_host) *total_host = base + all;
+        if (count_dev) *count_dev = base + all + 1;
+    }
 }
 
 // copy each segment slot to its place in the contiguous stream
@@ -2405,7 +2426,7 @@ static hipError_t launch_deflate_pipe(const DeflateArgs& A, uint32_t seg_bytes, 
 
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st,
                           hipEvent_t ev_main0, hipEvent_t ev_main1, bool dict, const uint64_t* nseg_dev,
-                          const uint8_t* bflag, const DeflatePipe* pipe) {
+                          const uint8_t* bflag, const DeflatePipe* pipe, uint64_t* total_host) {
     if (dict && (!A.btab || seg_bytes != 32768)) return hipErrorInvalidValue;
     if (pipe && (A.btab || A.level < 2 || seg_bytes < 32768 || A.dbg || !pipe->chunk || pipe->chunk >= A.nseg))
         return hipErrorInvalidValue;
@@ -2416,7 +2437,7 @@ hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t 
         hipError_t e = launch_deflate_pipe(A, seg_bytes, st, *pipe);
         if (e != hipSuccess) return e;
         if (ev_main1) (void)hipEventRecord(ev_main1, st);
-        e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st);
+        e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st, total_host);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_compact, dim3((uint32_t)((A.nseg + 3) / 4)), dim3(256), 0, st, A.slots, A.slot_bytes,
                            A.sizes, A.offsets, A.nseg, A.out, A.cap);
@@ -2447,7 +2468,7 @@ hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t 
             else hipLaunchKernelGGL((k_deflate_emit_batch<16384, false>), dim3(eg), dim3(64 * EM_NW), 0, st, B);
         }
         if (ev_main1) (void)hipEventRecord(ev_main1, st);
-        const hipError_t e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st);
+        const hipError_t e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st, total_host);
         if (e != hipSuccess) return e;
         const uint64_t waves = A.nseg + (A.nbuf + 63) / 64;
         hipLaunchKernelGGL(k_compact_batch, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, st, B);
@@ -2486,7 +2507,7 @@ hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t 
     }
     if (ev_main1) (void)hipEventRecord(ev_main1, st);
     {
-        const hipError_t e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st);
+        const hipError_t e = launch_scan_u32(A.sizes, A.offsets, A.nseg, A.total, st, total_host);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_compact, dim3((uint32_t)((A.nseg + 3) / 4)), dim3(256), 0, st, A.slots, A.slot_bytes,
@@ -2497,11 +2518,12 @@ hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t 
 // the block sums go to offs[n + 1 ..] (offs holds scan_words(n) entries; offs[n] may be total)
 uint64_t scan_words(uint64_t n) { return n + 2 + (n + SCAN_BLK - 1) / SCAN_BLK; }
 hipError_t launch_scan_u32(const uint32_t* v, uint64_t* offs, uint64_t n, uint64_t* total,
-                           hipStream_t st) {
+                           hipStream_t st, uint64_t* total_host, uint64_t* count_dev) {
     const uint64_t nb = n ? (n + SCAN_BLK - 1) / SCAN_BLK : 1;
-    uint64_t* partial = offs + n + 1;
-    if (nb > 1) hipLaunchKernelGGL(k_scan_part, dim3((uint32_t)nb), dim3(SCAN_NT), 0, st, v, n, partial);
-    hipLaunchKernelGGL(k_scan_apply, dim3((uint32_t)nb), dim3(SCAN_NT), 0, st, v, n, partial, offs, total);
+    const uint64_t* partial = nb > SCAN_ONE ? offs + n + 1 : nullptr;
+    if (partial) hipLaunchKernelGGL(k_scan_part, dim3((uint32_t)nb), dim3(SCAN_NT), 0, st, v, n, offs + n + 1);
+    hipLaunchKernelGGL(k_scan_apply, dim3((uint32_t)nb), dim3(SCAN_NT), 0, st, v, n, partial, offs, total, total_host,
+                       count_dev);
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 
 #include "../../include/dmx.h"
 #include "dmx_internal.h"
+#include "inflate_plan.h"
 
 namespace dmx {
 
@@ -41,6 +42,15 @@ struct DevBuf {
     }
     template <class T>
     T* as() const { return static_cast<T*>(p); }
+};
+
+// The synchronous calls' results, in pinned host memory mapped into the device: the kernels
+// that produce these words store them here too, and the host reads them after the call's one
+// hipStreamSynchronize -- no copy operation.  (The device-side copies in Scal stay: kernels read them.)
+struct HostRes {
+    uint64_t total;     // deflate: the stream's length (k_scan_apply)
+    uint64_t nmarkers;  // inflate: the marker scan's total (k_scan_apply)
+    InflateResult res;  // inflate: the last validation (k_inflate_validate)
 };
 
 }  // namespace dmx
@@ -83,7 +93,11 @@ struct dmx_ctx {
     // the chain scratch (tile counts, candidates, jump tables, member table); descriptors + results
     // (bgzt: the candidate scan's tile counts and offsets, which outlive the sizing of bgzc)
     DevBuf bgzs, bgzc, bgzd, bgzt;
+    dmx::HostRes* hres = nullptr;      // host address (nullptr: not available, results are copied)
+    dmx::HostRes* hres_dev = nullptr;  // the same block as the device sees it
+    dmx::SpecKnob spec = dmx::SpecKnob::On;  // DMX_INFLATE_SPEC, read at dmx_create
     bool timing = false;
+    bool ev3_marked = false;  // ev[3] is recorded already, in front of the call's last wait (mark_end)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_df = nullptr;          // end of the last deflate's work (its scratch is reused)
     hipEvent_t ev_inf = nullptr;         // end of the last asynchronous inflate's work
@@ -109,6 +123,7 @@ namespace dmx {
 //   DMX_RECS=1        segmented inflate: per-candidate outcome of each pass on stderr
 // A developer switch of its own, read at every dmx_create (deflate_pipe.h: pipe_knob):
 //   DMX_DEFLATE_PIPE=0|1|<chunks>|s<segments>  the deflate's chunk pipeline
+//   DMX_INFLATE_SPEC=0|1|force  the synchronous inflate's speculative first pass (inflate_plan.h)
 enum : uint32_t { DIAG_PHASES = 1, DIAG_FB = 2, DIAG_RECS = 4, DIAG_DEBUG = 8, DIAG_FBT = 16 };
 struct Diag {
     uint32_t bits = 0;
@@ -143,6 +158,9 @@ uint64_t* phase_buf(dmx_ctx* c, uint64_t nidx);
 void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st, uint64_t stride = 0);
 
 void begin_timing(dmx_ctx* c, hipStream_t st);
+// mark_end in front of the call's last hipStreamSynchronize records the end event there, so that
+// end_timing behind it reads the times without a wait of its own
+void mark_end(dmx_ctx* c, hipStream_t st);
 void end_timing(dmx_ctx* c, hipStream_t st);
 
 // the stream seen as aligned words (the kernels read 4-byte words at or below its start)
@@ -156,7 +174,11 @@ struct StreamWords {
 // host_inflate.cpp
 // candidate segment starts: counts the markers per tile and scans the counts (Scal::nmarkers
 // receives the total, nothing waits); then marker_write lists bit 0 and the markers in c->cands
-int marker_scan(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t* ntiles, hipStream_t st);
+// sync_call: the synchronous inflate's -- the count kernel zeroes the validation words and the
+// heavy list's counters (*hl_zeroed: the list was there to zero), the total goes to the host
+// block too and the candidate count to Scal::ncand
+int marker_scan(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t* ntiles, hipStream_t st, bool sync_call = false,
+                const uint32_t** hl_zeroed = nullptr);
 int marker_write(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t ntiles, uint64_t cand_cap, hipStream_t st);
 // Shared inflate driver.  fixed_out != nullptr: decode into the caller's device buffer of
 // `cap` bytes.  Otherwise decode into c->out, grown as needed (*dev_out receives it).

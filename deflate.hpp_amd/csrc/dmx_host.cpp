@@ -111,12 +111,21 @@ void phase_dump(dmx_ctx* c, const char* kernel, uint64_t nidx, hipStream_t st, u
 
 void begin_timing(dmx_ctx* c, hipStream_t st) {
     c->stats = dmx_stats{};
+    c->ev3_marked = false;
     if (c->timing) (void)hipEventRecord(c->ev[0], st);
+}
+void mark_end(dmx_ctx* c, hipStream_t st) {
+    if (!c->timing) return;
+    (void)hipEventRecord(c->ev[3], st);
+    c->ev3_marked = true;
 }
 void end_timing(dmx_ctx* c, hipStream_t st) {
     if (!c->timing) return;
-    (void)hipEventRecord(c->ev[3], st);
-    (void)hipEventSynchronize(c->ev[3]);
+    if (!c->ev3_marked) {  // (marked: recorded in front of the wait the caller has just done)
+        (void)hipEventRecord(c->ev[3], st);
+        (void)hipEventSynchronize(c->ev[3]);
+    }
+    c->ev3_marked = false;
     float a = 0, b = 0;
     (void)hipEventElapsedTime(&a, c->ev[0], c->ev[3]);
     (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
@@ -220,15 +229,20 @@ int deflate_device_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, int level, 
         if (P.chunk && !pipe_streams(c)) return DMX_ERR_DEVICE;
         P.side = c->side, P.ev_chunk = c->ev_chunk, P.ev_side = c->ev_side;
     }
+    // the synchronous call reads the length from the host result block (k_scan_apply stores it
+    // there too): no copy operation behind the work
+    uint64_t* const total_host = (!async && c->hres) ? &c->hres_dev->total : nullptr;
     HIPCHK(launch_deflate(A, c->seg, st, tm ? c->ev[1] : nullptr, tm ? c->ev[2] : nullptr, false, nullptr, nullptr,
-                          P.chunk ? &P : nullptr));
+                          P.chunk ? &P : nullptr, total_host));
     HIPCHK(hipEventRecord(c->ev_df, st));
     c->df_pending = true;
     if (async) return DMX_OK;
     if (A.dbg) phase_dump(c, "deflate", nseg, st, c->seg == 65536 ? 0 : std::min<uint64_t>(nseg, deflate_front_fit(c->seg)));
     uint64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, A.total, 8, hipMemcpyDeviceToHost, st));
+    if (!total_host) HIPCHK(hipMemcpyAsync(&total, A.total, 8, hipMemcpyDeviceToHost, st));
+    mark_end(c, st);
     HIPCHK(hipStreamSynchronize(st));
+    if (total_host) total = c->hres->total;
     end_timing(c, st);
     c->stats.segments = nseg;
     c->stats.in_bytes = n;
@@ -876,6 +890,7 @@ int dmx_create(dmx_ctx** out, const dmx_config* cfg) {
     c->heavy_bytes = cfg->dev_heavy_bytes;
     c->diag = diag_env().bits;
     c->pipe = pipe_knob(std::getenv("DMX_DEFLATE_PIPE"));
+    c->spec = spec_knob(std::getenv("DMX_INFLATE_SPEC"));
     if (hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c->ncu <= 0)
         c->ncu = 256;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -883,6 +898,20 @@ int dmx_create(dmx_ctx** out, const dmx_config* cfg) {
         return DMX_ERR_DEVICE;
     }
     for (auto& e : c->ev) (void)hipEventCreate(&e);
+    // the host result block (dmx_ctx.h); without it the calls copy their results as before
+    {
+        void *h = nullptr, *d = nullptr;
+        if (hipHostMalloc(&h, sizeof(HostRes), hipHostMallocMapped) == hipSuccess) {
+            if (hipHostGetDevicePointer(&d, h, 0) == hipSuccess && d) {
+                std::memset(h, 0, sizeof(HostRes));
+                c->hres = static_cast<HostRes*>(h);
+                c->hres_dev = static_cast<HostRes*>(d);
+            } else {
+                (void)hipHostFree(h);
+            }
+        }
+        (void)hipGetLastError();
+    }
     if (hipEventCreateWithFlags(&c->ev_df, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_inf, hipEventDisableTiming) != hipSuccess) {
         dmx_destroy(c);
@@ -933,6 +962,7 @@ void dmx_destroy(dmx_ctx* c) {
         (void)hipEventDestroy(c->ev_side);
     }
     if (c->fbkeep_h) (void)hipHostFree(c->fbkeep_h);
+    if (c->hres) (void)hipHostFree(c->hres);
     if (c->pin) (void)hipHostFree(c->pin);
     (void)hipStreamDestroy(c->stream);
     delete c;

@@ -80,7 +80,8 @@ static_assert(deflate_tok_stride(32768) == 17632 && deflate_tok_stride(16384) ==
 // pipe: the chunk pipeline (single stream, levels 2-3, 32 or 64 KiB segments, no DMX_PHASES)
 hipError_t launch_deflate(const DeflateArgs& A, uint32_t seg_bytes, hipStream_t st, hipEvent_t ev0,
                           hipEvent_t ev1, bool dict = false, const uint64_t* nseg_dev = nullptr,
-                          const uint8_t* bflag = nullptr, const DeflatePipe* pipe = nullptr);
+                          const uint8_t* bflag = nullptr, const DeflatePipe* pipe = nullptr,
+                          uint64_t* total_host = nullptr);
 // the front kernel's persistent workgroups that fit the GPU at once: workgroup b takes the
 // segments b, b + grid, ... with grid = min(segments, this)
 uint64_t deflate_front_fit(uint32_t seg_bytes);
@@ -135,8 +136,12 @@ struct InflateResult {
                          // offsets, literals + copies, flush + refill, steps
 };
 
+// zero_w / zero_hl (each or nullptr): validation words and the heavy list's two counters that
+// block 0 zeroes, for the kernels that follow in the same call
+struct ValidateWords;
 hipError_t launch_marker_count(const uint32_t* in_words, uint64_t misalign, uint64_t n,
-                               uint32_t* tile_counts, uint64_t ntiles, hipStream_t st);
+                               uint32_t* tile_counts, uint64_t ntiles, hipStream_t st,
+                               ValidateWords* zero_w = nullptr, uint32_t* zero_hl = nullptr);
 // cands holds cand_cap entries: candidates past them are not written (the async inflate sizes
 // its scratch before the count is known)
 hipError_t launch_marker_write(const uint32_t* in_words, uint64_t misalign, uint64_t n,
@@ -151,8 +156,10 @@ uint64_t marker_tiles(uint64_t n, uint64_t misalign);
 // exclusive scan of n values into offs (64-bit) and *total; offs must hold scan_words(n)
 // entries (the block sums of the multi-workgroup scan follow the n offsets)
 uint64_t scan_words(uint64_t n);
+// total_host: host-mapped memory that receives the total too (the host reads it after its wait);
+// count_dev: a device word that receives total + 1 (a marker scan's candidate count)
 hipError_t launch_scan_u32(const uint32_t* v, uint64_t* offs, uint64_t n, uint64_t* total,
-                           hipStream_t st);
+                           hipStream_t st, uint64_t* total_host = nullptr, uint64_t* count_dev = nullptr);
 hipError_t launch_inflate_segments(const InflateArgs& A, hipStream_t st, hipEvent_t ev0,
                                    hipEvent_t ev1);
 // workgroup-per-segment decoder (lane-parallel Huffman decode + pointer-jumping LZ77);
@@ -164,22 +171,25 @@ hipError_t launch_inflate_pj(const InflateArgs& A, uint32_t seg, hipStream_t st,
 // min(ncand * 16404, 8 * n + 20 * ncand) words; tokoff ncand + 1, ntok / caps ncand entries.
 // heavy != 0: when at most `limit` candidates span more than `heavy` bytes (counted on the
 // device into hl[1]), those are declined and listed in hl (hl[0] = count, the indices from
-// hl[2] on; ncand + 2 words) for launch_inflate_pj_list.
+// hl[2] on; ncand + 2 words) for launch_inflate_pj_list.  hl_zeroed: hl[0..1] are zero already
+// (launch_marker_count), no fill is launched.
 // split: ncand words when A.slot is 64 KiB (the halves' split), else unused; ncu: the device's
 // compute units (the grid of the one-wave resolve)
 hipError_t launch_inflate_lanes(const InflateArgs& A, uint32_t* tok, uint64_t* tokoff,
                                 uint32_t* ntok, uint32_t* caps, uint32_t heavy, uint32_t limit,
                                 uint32_t* hl, uint32_t* split, int ncu, hipStream_t st, hipEvent_t ev0,
-                                hipEvent_t ev1);
+                                hipEvent_t ev1, bool hl_zeroed = false);
 // mode 6: the workgroup decoder over the candidates listed in hl, `grid` persistent workgroups
 hipError_t launch_inflate_pj_list(const InflateArgs& A, uint32_t seg, const uint32_t* hl, uint32_t grid,
                                   hipStream_t st, hipEvent_t ev1);
-// validation scratch: five device words, zeroed by the launch
+// validation scratch: five device words, zeroed by the launch (zeroed: an earlier kernel of the
+// call has done that, launch_marker_count); res_host: host-mapped memory that receives the
+// result too, or nullptr
 struct ValidateWords {
     unsigned long long kmin, bmin, umin, xmin, xcnt;
 };
 hipError_t launch_inflate_validate(const InflateArgs& A, ValidateWords* W, InflateResult* res,
-                                   hipStream_t st);
+                                   hipStream_t st, bool zeroed = false, InflateResult* res_host = nullptr);
 
 // block-parallel inflate of arbitrary streams (inflate_blocks.hip, path 5; FbUnit and the unit
 // stops and code states: inflate_records.h)

@@ -9,11 +9,21 @@
 
 namespace dmx {
 
-int marker_scan(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t* ntiles, hipStream_t st) {
+int marker_scan(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t* ntiles, hipStream_t st, bool sync_call,
+                const uint32_t** hl_zeroed) {
     const uint64_t nt = *ntiles = marker_tiles(n, w.misalign);
     if (!c->tiles.ensure(nt * 4) || !c->tileoffs.ensure(scan_words(nt) * 8)) return DMX_ERR_NOMEM;
-    HIPCHK(launch_marker_count(w.words, w.misalign, n, c->tiles.as<uint32_t>(), nt, st));
-    HIPCHK(launch_scan_u32(c->tiles.as<uint32_t>(), c->tileoffs.as<uint64_t>(), nt, &c->scal.as<Scal>()->nmarkers, st));
+    Scal* ds = c->scal.as<Scal>();
+    if (!sync_call) {
+        HIPCHK(launch_marker_count(w.words, w.misalign, n, c->tiles.as<uint32_t>(), nt, st));
+        HIPCHK(launch_scan_u32(c->tiles.as<uint32_t>(), c->tileoffs.as<uint64_t>(), nt, &ds->nmarkers, st));
+        return DMX_OK;
+    }
+    uint32_t* const hl = c->lheavy.as<uint32_t>();  // (nullptr before the first heavy route)
+    if (hl_zeroed) *hl_zeroed = hl;
+    HIPCHK(launch_marker_count(w.words, w.misalign, n, c->tiles.as<uint32_t>(), nt, st, &ds->vw, hl));
+    HIPCHK(launch_scan_u32(c->tiles.as<uint32_t>(), c->tileoffs.as<uint64_t>(), nt, &ds->nmarkers, st,
+                           c->hres ? &c->hres_dev->nmarkers : nullptr, &ds->ncand));
     return DMX_OK;
 }
 int marker_write(dmx_ctx* c, const StreamWords& w, size_t n, uint64_t ntiles, uint64_t cand_cap, hipStream_t st) {
@@ -54,10 +64,10 @@ bool lane_bufs(dmx_ctx* c, uint64_t ncand, size_t n) {
            c->lntok.ensure(ncand * 4) && c->lcaps.ensure(ncand * 4) && c->lsplit.ensure(ncand * 4 + 8);
 }
 int lanes_pass(dmx_ctx* c, const InflateArgs& A, uint32_t heavy, uint32_t heavy_limit, uint32_t* hl, hipStream_t st,
-               hipEvent_t e0, hipEvent_t e1) {
+               hipEvent_t e0, hipEvent_t e1, bool hl_zeroed = false) {
     HIPCHK(launch_inflate_lanes(A, c->ltok.as<uint32_t>(), c->ltokoff.as<uint64_t>(), c->lntok.as<uint32_t>(),
                                 c->lcaps.as<uint32_t>(), heavy, heavy_limit, hl, c->lsplit.as<uint32_t>(), c->ncu, st,
-                                e0, e1));
+                                e0, e1, hl_zeroed));
     return DMX_OK;
 }
 
@@ -116,6 +126,12 @@ struct PlanRun {
     InflateArgs A;  // out / cap: where the passes decode to
     PassPlan plan;
     uint32_t lead_mode = 0;  // the last pass run that decodes every candidate (not a patch pass)
+    int first = 0;           // the pass to start from (> 0: r holds the validation of the pass before)
+    bool one_pass = false;   // stop behind the first pass run (the speculative pass)
+    // the call's marker count kernel has zeroed the validation words / the heavy list's counters
+    // (marker_scan); used up by the first pass run
+    bool vw_zeroed = false;
+    const uint32_t* hl_zeroed = nullptr;
 };
 
 // the plan's passes into A.out / A.cap; r: the last validation result
@@ -124,8 +140,8 @@ int run_plan(PlanRun& s, InflateResult& r) {
     hipStream_t st = s.st;
     InflateArgs& A = s.A;
     Scal* ds = c->scal.as<Scal>();
-    r.status = 2;
-    for (int pi = 0; pi < s.plan.np; pi++) {
+    if (s.first == 0) r.status = 2;
+    for (int pi = s.first; pi < s.plan.np; pi++) {
         const uint32_t mode = s.plan.pass[pi][0];
         if (pass_skipped(mode, r.exotic, A.ncand)) continue;
         A.mode = mode;
@@ -134,7 +150,8 @@ int run_plan(PlanRun& s, InflateResult& r) {
         hipEvent_t e0 = (c->timing && pi == 0) ? c->ev[1] : nullptr, e1 = c->timing ? c->ev[2] : nullptr;
         if (mode != 3 && mode != 6) s.lead_mode = mode;
         if (mode == 4) {
-            if (lanes_pass(c, A, s.plan.heavy, s.plan.heavy_limit, c->lheavy.as<uint32_t>(), st, e0, e1) != DMX_OK)
+            uint32_t* const hl = c->lheavy.as<uint32_t>();
+            if (lanes_pass(c, A, s.plan.heavy, s.plan.heavy_limit, hl, st, e0, e1, hl && hl == s.hl_zeroed) != DMX_OK)
                 return DMX_ERR_DEVICE;
         } else if (mode == 6) {
             const uint32_t grid = (uint32_t)std::min<uint64_t>(r.exotic, (uint64_t)std::max(c->ncu, 1));
@@ -146,12 +163,17 @@ int run_plan(PlanRun& s, InflateResult& r) {
             HIPCHK(hipMemsetAsync(&ds->ticket, 0, 4, st));
             HIPCHK(launch_inflate_segments(A, st, e0, e1));
         }
-        HIPCHK(launch_inflate_validate(A, &ds->vw, &ds->res, st));
+        // the result comes through the host result block (k_inflate_validate stores it there too)
+        HIPCHK(launch_inflate_validate(A, &ds->vw, &ds->res, st, s.vw_zeroed, c->hres ? &c->hres_dev->res : nullptr));
+        s.vw_zeroed = false;
+        s.hl_zeroed = nullptr;
         if (A.dbg) phase_dump(c, "inflate", A.ncand, st);
-        HIPCHK(hipMemcpyAsync(&r, &ds->res, sizeof r, hipMemcpyDeviceToHost, st));
+        if (!c->hres) HIPCHK(hipMemcpyAsync(&r, &ds->res, sizeof r, hipMemcpyDeviceToHost, st));
+        mark_end(c, st);  // (the last pass's stands: end_timing does not wait again)
         HIPCHK(hipStreamSynchronize(st));
+        if (c->hres) r = c->hres->res;
         if (c->diag & DIAG_RECS) dump_recs(A, r.status);
-        if (pass_ends_plan(mode, s.lead_mode, r.status, r.exotic)) break;
+        if (s.one_pass || pass_ends_plan(mode, s.lead_mode, r.status, r.exotic)) break;
     }
     return DMX_OK;
 }
@@ -216,6 +238,7 @@ int chain_repair(PlanRun& s, bool fixed, uint8_t* out, size_t cap, size_t* total
     HIPCHK(launch_place_segments(src, (uint32_t)slot, dch, doffs, dsz, nch, place, st));
     if (place != out && ch.total) HIPCHK(hipMemcpyAsync(out, place, ch.total, hipMemcpyDeviceToDevice, st));
     if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    mark_end(c, st);
     HIPCHK(hipStreamSynchronize(st));
     end_timing(c, st);
     c->last_end = h[ch.chain.back()].end_byte;
@@ -277,6 +300,44 @@ int inflate_serial(dmx_ctx* c, InflateArgs A, size_t n, uint8_t* fixed_out, size
     return r.status;
 }
 
+// What follows the plan's passes (r: the last validation): the decoded stream's figures, or the
+// chain repair, path 5 and the serial decoder.  out / cap: where the passes decoded to.
+int inflate_finish(dmx_ctx* c, PlanRun& s, const InflateResult& r, const uint8_t* d_in, size_t n, uint8_t* fixed_out,
+                   uint8_t* out, size_t cap, bool parallel_ok, size_t* total_out, uint8_t** dev_out, uint32_t iflags) {
+    hipStream_t st = s.st;
+    const uint64_t ncand = s.A.ncand;
+    c->stats.segments = ncand;
+    c->stats.in_bytes = n;
+    if (r.status == 0) {
+        end_timing(c, st);
+        c->last_end = r.end_byte;
+        c->stats.path = s.lead_mode == 4 ? 4 : s.lead_mode >= 2 ? 3 : s.lead_mode;
+        c->stats.out_bytes = r.total;
+        *total_out = r.total;
+        if (dev_out) *dev_out = out;
+        return r.total > cap ? DMX_ERR_CAPACITY : DMX_OK;
+    }
+    c->ev3_marked = false;  // (the paths below wait again: their end_timing records the end)
+    if (s.lead_mode == 4 && parallel_ok && ncand > 1) {
+        bool repaired = false;
+        const int rc = chain_repair(s, fixed_out != nullptr, out, cap, total_out, dev_out, &repaired);
+        if (rc != DMX_OK || repaired) return rc;
+    }
+    c->ev3_marked = false;
+    if (c->inflate_pass == -1 || c->inflate_pass == 5) {
+        bool handled = false;
+        const int rc = inflate_fb_locked(c, d_in, n, fixed_out, cap, total_out, dev_out, st, &handled, iflags);
+        if (handled) {
+            end_timing(c, st);
+            c->stats.path = 5;
+            c->stats.in_bytes = n;
+            c->stats.out_bytes = *total_out;
+            return rc;
+        }
+    }
+    return inflate_serial(c, s.A, n, fixed_out, cap, total_out, dev_out, st);
+}
+
 }  // namespace
 
 int inflate_device_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8_t* fixed_out, size_t cap,
@@ -289,11 +350,64 @@ int inflate_device_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8_t* fi
     if (!c->scal.ensure(sizeof(Scal))) return DMX_ERR_NOMEM;
     const StreamWords w(d_in);
 
+    Scal* const ds = c->scal.as<Scal>();
+
+    // The speculative first pass (inflate_plan.h): into a caller's buffer whose size says the lane
+    // decoder comes first, the marker list, the lane pass and its validation are launched for the
+    // provisioned count before the count is known, and the call waits once.
+    uint64_t ncap = 0;
+    PassPlan splan{};
+    bool spec = c->hres && spec_wanted(c->spec, fixed_out != nullptr, (iflags & DMX_IFLAG_PIECE) != 0,
+                                       (c->diag & (DIAG_PHASES | DIAG_RECS)) != 0, c->inflate_pass, c->seg, cap);
+    if (spec) {
+        ncap = spec_provision(c->seg, cap, n);
+        spec = cand_bufs(c, ncap);
+        if (spec) splan = make_plan(c, n, ncap, true);
+        spec = spec && splan.np > 0 && splan.pass[0][0] == 4;
+    }
+
     // candidate segment starts
     uint64_t ntiles = 0, nmarkers = 0;
-    if (const int rc = marker_scan(c, w, n, &ntiles, st); rc != DMX_OK) return rc;
-    HIPCHK(hipMemcpyAsync(&nmarkers, &c->scal.as<Scal>()->nmarkers, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    const uint32_t* hl_zeroed = nullptr;
+    if (const int rc = marker_scan(c, w, n, &ntiles, st, true, &hl_zeroed); rc != DMX_OK) return rc;
+    bool vw_zeroed = true;
+    if (spec) {
+        if (marker_write(c, w, n, ntiles, ncap, st) != DMX_OK) return DMX_ERR_DEVICE;
+        PlanRun s{c, st, inflate_args(c, w, n, ncap, fixed_out, cap, iflags), splan};
+        s.A.ncand_dev = &ds->ncand;
+        s.one_pass = true;
+        s.vw_zeroed = true;
+        s.hl_zeroed = hl_zeroed;
+        InflateResult r{};
+        if (const int rc = run_plan(s, r); rc != DMX_OK) return rc;
+        vw_zeroed = false, hl_zeroed = nullptr;  // used up
+        nmarkers = c->hres->nmarkers;
+        const uint64_t ncand = nmarkers + 1;
+        const PassPlan classic = ncand <= ncap ? make_plan(c, n, ncand, true) : PassPlan{};
+        const SpecVerdict v = spec_decide(splan, classic, ncand, ncap, r.status, r.exotic);
+        if (v != SpecVerdict::Discard) {
+            // the pass stands as the classic plan's first: the rest of that plan, then as ever
+            s.A.ncand = ncand;
+            s.A.ncand_dev = nullptr;
+            s.plan = classic;
+            s.one_pass = false;
+            if (v == SpecVerdict::Continue) {
+                s.first = 1;
+                if (const int rc = run_plan(s, r); rc != DMX_OK) return rc;
+                s.first = 0;
+            }
+            return inflate_finish(c, s, r, d_in, n, fixed_out, fixed_out, cap, true, total_out, dev_out, iflags);
+        }
+        // discarded: today's flow from the marker list on (the count is known, the tile offsets stand)
+    } else {
+        if (c->hres) {
+            HIPCHK(hipStreamSynchronize(st));
+            nmarkers = c->hres->nmarkers;
+        } else {
+            HIPCHK(hipMemcpyAsync(&nmarkers, &ds->nmarkers, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
     const uint64_t ncand = nmarkers + 1;
     if (!cand_bufs(c, ncand)) return DMX_ERR_NOMEM;
     if (marker_write(c, w, n, ntiles, ~0ull, st) != DMX_OK) return DMX_ERR_DEVICE;
@@ -320,36 +434,11 @@ int inflate_device_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8_t* fi
     PlanRun s{c, st, inflate_args(c, w, n, ncand, out, cap, iflags), PassPlan{}};
     s.A.dbg = phase_buf(c, ncand);
     s.plan = make_plan(c, n, ncand, parallel_ok);
+    s.vw_zeroed = vw_zeroed;
+    s.hl_zeroed = hl_zeroed;  // (make_plan may have moved the list: run_plan compares)
     InflateResult r{};
     if (const int rc = run_plan(s, r); rc != DMX_OK) return rc;
-    c->stats.segments = ncand;
-    c->stats.in_bytes = n;
-    if (r.status == 0) {
-        end_timing(c, st);
-        c->last_end = r.end_byte;
-        c->stats.path = s.lead_mode == 4 ? 4 : s.lead_mode >= 2 ? 3 : s.lead_mode;
-        c->stats.out_bytes = r.total;
-        *total_out = r.total;
-        if (dev_out) *dev_out = out;
-        return r.total > cap ? DMX_ERR_CAPACITY : DMX_OK;
-    }
-    if (s.lead_mode == 4 && parallel_ok && ncand > 1) {
-        bool repaired = false;
-        const int rc = chain_repair(s, fixed_out != nullptr, out, cap, total_out, dev_out, &repaired);
-        if (rc != DMX_OK || repaired) return rc;
-    }
-    if (c->inflate_pass == -1 || c->inflate_pass == 5) {
-        bool handled = false;
-        const int rc = inflate_fb_locked(c, d_in, n, fixed_out, cap, total_out, dev_out, st, &handled, iflags);
-        if (handled) {
-            end_timing(c, st);
-            c->stats.path = 5;
-            c->stats.in_bytes = n;
-            c->stats.out_bytes = *total_out;
-            return rc;
-        }
-    }
-    return inflate_serial(c, s.A, n, fixed_out, cap, total_out, dev_out, st);
+    return inflate_finish(c, s, r, d_in, n, fixed_out, out, cap, parallel_ok, total_out, dev_out, iflags);
 }
 
 // dmx_inflate_device_async: the lane path (path 4) of a libdmx-layout stream with no host

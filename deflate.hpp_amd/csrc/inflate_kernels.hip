@@ -92,9 +92,16 @@ __device__ __forceinline__ uint32_t mk_scan16(const uint32_t* w, uint64_t misali
     return mask;
 }
 
+// (zero_w / zero_hl, each or nullptr: the validation words and the heavy list's two counters, which
+// the kernels later in the same call expect zeroed -- a fill launch of their own otherwise)
 __global__ __launch_bounds__(MK_NT) void k_marker_count(const uint32_t* w, uint64_t misalign,
-                                                        uint64_t n, uint32_t* tile_counts) {
+                                                        uint64_t n, uint32_t* tile_counts, ValidateWords* zero_w,
+                                                        uint32_t* zero_hl) {
     __shared__ uint32_t red[MK_NT / 64];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (zero_w) *zero_w = ValidateWords{0, 0, 0, 0, 0};
+        if (zero_hl) zero_hl[0] = zero_hl[1] = 0;
+    }
     const uint64_t g = (uint64_t)blockIdx.x * MK_NT + threadIdx.x;
     const uint32_t c = __popc(mk_scan16(w, misalign, n, g));
     const uint32_t s = wave_sum(c);
@@ -130,9 +137,10 @@ uint64_t marker_tiles(uint64_t n, uint64_t misalign) {
 }
 
 hipError_t launch_marker_count(const uint32_t* in_words, uint64_t misalign, uint64_t n,
-                               uint32_t* tile_counts, uint64_t ntiles, hipStream_t st) {
+                               uint32_t* tile_counts, uint64_t ntiles, hipStream_t st, ValidateWords* zero_w,
+                               uint32_t* zero_hl) {
     hipLaunchKernelGGL(k_marker_count, dim3((uint32_t)ntiles), dim3(MK_NT), 0, st, in_words,
-                       misalign, n, tile_counts);
+                       misalign, n, tile_counts, zero_w, zero_hl);
     return hipGetLastError();
 }
 
@@ -904,27 +912,36 @@ __global__ __launch_bounds__(256) void k_inflate_validate_scan(InflateArgs A, Va
     }
 }
 
-__global__ void k_inflate_validate(InflateArgs A, const ValidateWords* W, InflateResult* res) {
+// (res_host, or nullptr: the context's host-mapped result block gets the same words in plain
+// stores -- the host reads them after its wait, no copy operation)
+__global__ void k_inflate_validate(InflateArgs A, const ValidateWords* W, InflateResult* res,
+                                   InflateResult* res_host) {
     auto unmax = [](unsigned long long v) -> uint64_t { return v ? ~v : ~0ull; };
     const uint64_t k = unmax(W->kmin), bmin = unmax(W->bmin), umin = unmax(W->umin), xmin = unmax(W->xmin);
+    const uint64_t nc = cand_count(A);
+    int32_t status = 2;
+    uint64_t total = 0;
+    if (xmin < nc) {
+        status = 1;
+    } else if (k < nc && bmin > k) {
+        status = (A.mode != 1 && umin < k) ? 1 : 0;
+    }
+    uint64_t end_byte = 0;
+    if (status == 0) {
+        total = A.recs[k].offset + A.recs[k].out_size;
+        end_byte = A.recs[k].end_byte;
+    }
     res->fin_index = (uint32_t)k;
     res->exotic = W->xcnt;
-    const uint64_t nc = cand_count(A);
-    if (xmin < nc) {
-        res->status = 1;
-        res->total = 0;
-    } else if (k < nc && bmin > k) {
-        if (A.mode != 1 && umin < k) {
-            res->status = 1;
-            res->total = 0;
-        } else {
-            res->status = 0;
-            res->total = A.recs[k].offset + A.recs[k].out_size;
-            res->end_byte = A.recs[k].end_byte;
-        }
-    } else {
-        res->total = 0;
-        res->status = 2;
+    res->status = status;
+    res->total = total;
+    if (status == 0) res->end_byte = end_byte;
+    if (res_host) {
+        res_host->fin_index = (uint32_t)k;
+        res_host->exotic = W->xcnt;
+        res_host->status = status;
+        res_host->total = total;
+        res_host->end_byte = end_byte;
     }
 }
 
@@ -2174,11 +2191,13 @@ hipError_t launch_async_result(const InflateResult* res, const uint64_t* ncand, 
 }
 
 hipError_t launch_inflate_validate(const InflateArgs& A, ValidateWords* W, InflateResult* res,
-                                   hipStream_t st) {
-    hipError_t e = hipMemsetAsync(W, 0, sizeof(ValidateWords), st);
-    if (e != hipSuccess) return e;
+                                   hipStream_t st, bool zeroed, InflateResult* res_host) {
+    if (!zeroed) {
+        const hipError_t e = hipMemsetAsync(W, 0, sizeof(ValidateWords), st);
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(k_inflate_validate_scan, dim3((uint32_t)((A.ncand + 255) / 256)), dim3(256), 0, st, A, W);
-    hipLaunchKernelGGL(k_inflate_validate, dim3(1), dim3(1), 0, st, A, (const ValidateWords*)W, res);
+    hipLaunchKernelGGL(k_inflate_validate, dim3(1), dim3(1), 0, st, A, (const ValidateWords*)W, res, res_host);
     return hipGetLastError();
 }
 

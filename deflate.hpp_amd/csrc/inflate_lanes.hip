@@ -1251,10 +1251,12 @@ __global__ __launch_bounds__(NT) void k_inflate_resolve_half(InflateArgs A, Lane
     }
 }
 
-// number of dense candidates (*cnt zeroed by the caller)
+// number of dense candidates (*cnt zeroed by the caller; ncand_dev: the device-side count of a
+// pass launched before the host knows it, or nullptr)
 __global__ void k_heavy_count(const uint8_t* in, const uint64_t* cands, uint64_t ncand, uint64_t n, uint32_t heavy,
-                              uint32_t* cnt) {
+                              uint32_t* cnt, const uint64_t* ncand_dev) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ncand_dev && *ncand_dev < ncand) ncand = *ncand_dev;
     if (j >= ncand) return;
     const uint64_t nxt = j + 1 < ncand ? cands[j + 1] : n;
     const uint64_t b = __ballot(ln_dense(in, cands[j], n, nxt - cands[j], heavy));
@@ -1292,14 +1294,17 @@ hipError_t launch_place_segments(const uint8_t* src, uint32_t slot, const uint64
 hipError_t launch_inflate_lanes(const InflateArgs& A, uint32_t* tok, uint64_t* tokoff,
                                 uint32_t* ntok, uint32_t* caps, uint32_t heavy, uint32_t limit,
                                 uint32_t* hl, uint32_t* split, int ncu, hipStream_t st, hipEvent_t ev0,
-                                hipEvent_t ev1) {
+                                hipEvent_t ev1, bool hl_zeroed) {
     if (ev0) (void)hipEventRecord(ev0, st);
     const uint32_t g = (uint32_t)((A.ncand + 255) / 256);
     const uint8_t* const in = reinterpret_cast<const uint8_t*>(A.in_words) + A.misalign;  // stream byte 0
     if (heavy) {
-        const hipError_t e = hipMemsetAsync(hl, 0, 8, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_heavy_count, dim3(g), dim3(256), 0, st, in, A.cands, A.ncand, A.n, heavy, hl + 1);
+        if (!hl_zeroed) {
+            const hipError_t e = hipMemsetAsync(hl, 0, 8, st);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_heavy_count, dim3(g), dim3(256), 0, st, in, A.cands, A.ncand, A.n, heavy, hl + 1,
+                           A.ncand_dev);
     }
     const bool big = A.slot > LN_OUT_CAP;  // 64 KiB segments (config C4's blocks)
     hipLaunchKernelGGL(k_lane_caps, dim3(g), dim3(256), 0, st, in, A.cands, A.ncand, A.n, caps, heavy, limit, hl,

@@ -2,6 +2,7 @@
 #include "inflate_plan.h"
 
 #include <algorithm>
+#include <string_view>
 
 #include "../../include/dmx.h"
 
@@ -55,6 +56,32 @@ PassPlan inflate_pass_plan(uint32_t seg, uint64_t n, uint64_t ncand, int forced,
     if (ncand == 1 && n > 65536 && forced == -1) p.np = 0;
     if (forced == 5 || forced == 7) p.np = 0;  // 7: the serial decoder alone
     return p;
+}
+
+SpecKnob spec_knob(const char* e) {
+    if (!e) return SpecKnob::On;
+    const std::string_view s(e);
+    if (s == "0") return SpecKnob::Off;
+    if (s == "force") return SpecKnob::Force;
+    return SpecKnob::On;
+}
+
+bool spec_wanted(SpecKnob knob, bool fixed_out, bool piece, bool diag, int forced, uint32_t seg, uint64_t cap) {
+    if (knob == SpecKnob::Off || !fixed_out || piece || diag || seg == 0) return false;
+    if (!plan_wants_lanes(forced)) return false;
+    return knob == SpecKnob::Force || cap / seg > kSpecMinCands;
+}
+
+SpecVerdict spec_decide(const PassPlan& spec, const PassPlan& classic, uint64_t ncand, uint64_t ncap, int32_t status,
+                        uint64_t exotic) {
+    if (ncand > ncap || ncand <= kSpecMinCands) return SpecVerdict::Discard;
+    if (spec.np == 0 || classic.np == 0 || spec.pass[0][0] != 4) return SpecVerdict::Discard;
+    if (classic.pass[0][0] != spec.pass[0][0] || classic.pass[0][1] != spec.pass[0][1] || classic.heavy != spec.heavy ||
+        classic.heavy_limit != spec.heavy_limit)
+        return SpecVerdict::Discard;
+    if (status == 0) return SpecVerdict::Accept;
+    if (status != 1) return SpecVerdict::Discard;  // nothing the segmented passes settle: as today, from the start
+    return pass_ends_plan(4, 4, status, exotic) ? SpecVerdict::Accept : SpecVerdict::Continue;
 }
 
 SegChain seg_chain_walk(const SegRecord* recs, const uint64_t* cands, uint64_t ncand) {

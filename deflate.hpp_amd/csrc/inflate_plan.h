@@ -53,6 +53,40 @@ inline bool pass_ends_plan(uint32_t mode, uint32_t lead_mode, int32_t status, ui
     return lead_mode == 4 && exotic == 0 && (mode == 4 || mode == 6 || mode == 3);
 }
 
+// ---- the speculative first pass of the synchronous inflate ---------------------------------
+// dmx_inflate_device into a caller's buffer launches the marker list, the lane pass and its
+// validation before the host knows the candidate count (the kernels stop at the device-side
+// count, as in dmx_inflate_device_async), so that the call waits for the GPU once.  The scratch
+// is provisioned for cap / segment + 64 candidates: a libdmx stream has one per segment.
+
+// DMX_INFLATE_SPEC (developer knob, read at dmx_create): "0" off, "1" (and unset or unparsable)
+// on, "force" on without the capacity gate, so that tests reach every branch at small sizes
+enum class SpecKnob : uint8_t { Off, On, Force };
+SpecKnob spec_knob(const char* e);
+// Up to this many candidates the first pass's heavy threshold and limit depend on the count
+// (inflate_pass_plan): no speculation at or below it.
+constexpr uint64_t kSpecMinCands = 2048;
+// (a marker is four bytes, so an n-byte stream has at most n / 4 + 1 candidates: a capacity far
+// above the stream's output does not size the scratch)
+inline uint64_t spec_provision(uint32_t seg, uint64_t cap, uint64_t n) {
+    const uint64_t by_cap = cap / seg + 64, by_n = n / 4 + 1;
+    return by_cap < by_n ? by_cap : by_n;
+}
+// Whether the call launches its first pass ahead of the count.  fixed_out: the caller supplies
+// the output buffer; piece: dmx_inflate_piece_device; diag: a diagnostic that sizes its buffers
+// by the count is on (DMX_PHASES, DMX_RECS); forced: dmx_config.dev_inflate_pass - 1.
+bool spec_wanted(SpecKnob knob, bool fixed_out, bool piece, bool diag, int forced, uint32_t seg, uint64_t cap);
+// What becomes of the speculative pass once the count and its validation are known.
+//   spec     the plan made for the provisioned count (its first pass is what ran)
+//   classic  the plan for the true count (np = 0 when ncand > ncap: not made)
+//   status / exotic: the pass's validation (InflateResult)
+// Discard: today's flow runs from the marker list on, as if nothing had been launched.
+// Accept: the pass stands as the classic plan's first pass and that plan is over (decoded, or a
+// layout the chain repair takes).  Continue: it stands, the classic plan goes on from its second pass.
+enum class SpecVerdict : uint8_t { Discard, Accept, Continue };
+SpecVerdict spec_decide(const PassPlan& spec, const PassPlan& classic, uint64_t ncand, uint64_t ncap, int32_t status,
+                        uint64_t exotic);
+
 // Path-4 chain repair: the walk from candidate 0 over the records of a lane pass.  Each
 // segment's end must be a candidate start, up to the first BFINAL; a flag other than
 // SEGF_FINAL on a chain member, or an end that is no candidate, ends it not ok.

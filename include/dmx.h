@@ -140,7 +140,9 @@ const char* dmx_strerror(int code);
 #define DMX_DEFLATE_NOT_FINAL 1u
 
 /* d_in/d_out are device pointers on the context's device; stream is a hipStream_t or NULL for
- * the context's own stream.  Returns DMX_ERR_CAPACITY if cap < the produced size. */
+ * the context's own stream.  Returns DMX_ERR_CAPACITY if cap < the produced size.
+ * Host synchronisations: 1 (the length, which the scan kernel stores into host-mapped memory:
+ * no copy operation follows the work). */
 int dmx_deflate_device(dmx_ctx* ctx, const void* d_in, size_t n, int level, uint32_t flags,
                        void* d_out, size_t cap, size_t* out_len, void* stream);
 
@@ -154,7 +156,14 @@ int dmx_deflate_device_async(dmx_ctx* ctx, const void* d_in, size_t n, int level
                              void* d_out, size_t cap, uint64_t* d_out_len, void* stream);
 
 /* Device-resident inflate.  Returns DMX_ERR_CAPACITY (and the needed size in *out_len) when
- * the decoded stream does not fit in cap. */
+ * the decoded stream does not fit in cap.
+ * Host synchronisations: 1 for a stream in libdmx's segment layout that the lane decoder takes
+ * whole, when cap / segment_bytes exceeds 2048 and the stream has more than 2048 and at most
+ * cap / segment_bytes + 64 segments -- the first pass is launched before the host knows the
+ * segment count, and the count and the pass's validation come back together (DMX_INFLATE_SPEC=0
+ * in the environment at dmx_create turns that off).  Otherwise 2 (segment count; validation),
+ * plus one per further pass of the plan and those of the chain repair, path 5 or the serial
+ * decoder where a stream needs them. */
 int dmx_inflate_device(dmx_ctx* ctx, const void* d_in, size_t n, void* d_out, size_t cap,
                        size_t* out_len, void* stream);
 
