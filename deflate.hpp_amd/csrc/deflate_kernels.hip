@@ -32,6 +32,7 @@
 // k_scan_part + k_scan_apply scan the per-segment sizes and k_compact concatenates the segment slots.
 #include "dmx_device.h"
 #include "dmx_internal.h"
+#include "huff_fit.h"
 
 namespace dmx {
 
@@ -42,11 +43,7 @@ constexpr int DF_CHUNK = 258;  // bytes per parse lane: one maximal match per ch
 constexpr int df_hash_bits(int seg) {  // hash bits of each of the two match tables: 11 at 16 KiB
     return seg >= 32768 ? 12 : 11;     // keeps that variant at <= 80 KiB of LDS (two per CU)
 }
-// Code-length limits of the emitted lit/len and distance codes.  RFC 1951 allows 15; 9 and 6
-// keep every code inside the one-level lookup tables of the lane decoder
-// (inflate_lanes.hip: 512 + 64 entries per segment in LDS) at < 1% ratio cost.
-constexpr int DF_LIT_MAXBITS = 9;
-constexpr int DF_DIST_MAXBITS = 6;
+// (the code-length limits DF_LIT_MAXBITS = 9, DF_DIST_MAXBITS = 6, DF_PRE_MAXBITS = 7: huff_fit.h)
 constexpr int DF_L3_DEPTH = 16;  // level 3: candidate-chain links searched per position
 constexpr uint32_t DF_L3_LONG = 16;  // level 3: a first link this long ends the chain search
 // Level 3: positions per match round (the level-2 rounds take 2 * DF_NT = 2048)
@@ -113,59 +110,8 @@ __device__ uint32_t block_excl_scan(uint32_t v, uint32_t* scratch, uint32_t* tot
 //     while the Kraft budget allows; repeat until the code is complete.
 // Zero or one used symbol -> two codes of length 1 (complete code, as zlib emits).
 // Stands in for FlatHuffmanTree::generateCodeLengths (common.hpp:322-404), a serial
-// priority-queue Huffman; this one stays within ~1% of optimal.
-// Kraft repair and slack fill on the class sizes cnt[1..15] of a code whose lengths are
-// non-decreasing in frequency rank: lengthen the last (least frequent) members of a class while
-// the code is over-full, then shorten the first (most frequent) members while slack remains.
-// Ends with a complete code (Kraft sum exactly 2^maxbits), as zlib and the reference require.
-__device__ __forceinline__ void fit_classes(uint32_t (&cnt)[17], int maxbits) {
-    // Kraft sums in units of 2^-maxbits (<= 288 * 2^8: 32-bit); every class weight is a power
-    // of two, so the divisions are shifts
-    const int32_t U = 1 << maxbits;
-    int32_t K = 0;
-#pragma unroll
-    for (int L = 1; L <= 15; L++) K += L <= maxbits ? (int32_t)cnt[L] << (maxbits - L) : 0;
-    while (K > U) {
-#pragma unroll
-        for (int L = 14; L >= 1; L--) {
-            if (L < maxbits && K > U && cnt[L]) {
-                const int sh = maxbits - L - 1;  // gain of one lengthening: 2^sh
-                const uint32_t need = (uint32_t)((K - U + (1 << sh) - 1) >> sh);
-                const uint32_t k = min(need, cnt[L]);
-                cnt[L] -= k;
-                cnt[L + 1] += k;
-                K -= (int32_t)k << sh;
-            }
-        }
-    }
-    uint32_t R = (uint32_t)(U - K);
-    for (int pass = 0; pass < 64 && R; pass++) {
-        bool changed = false;
-#pragma unroll
-        for (int L = 2; L <= 15; L++) {
-            if (L <= maxbits && cnt[L] && (1u << (maxbits - L)) <= R) {
-                const uint32_t k = min(cnt[L], R >> (maxbits - L));
-                cnt[L] -= k;
-                cnt[L - 1] += k;
-                R -= k << (maxbits - L);
-                changed = true;
-            }
-        }
-        if (!changed) break;
-    }
-}
-
-// initial length round(log2(F/f)) clamped to [1, maxbits] (0 for f == 0)
-__device__ __forceinline__ uint32_t init_len(uint32_t f, uint32_t F, int maxbits) {
-    if (!f) return 0;
-    // floor(log2(F / f)) without a division: F / f lies in [2^(e-1), 2^(e+1)) for e = the
-    // difference of the leading-bit positions, and is >= 2^e exactly when f << e <= F
-    const uint32_t e = (uint32_t)(__clz(f) - __clz(F));
-    const uint32_t L0 = e - (((uint64_t)f << e) > F ? 1u : 0u);
-    const uint64_t a = (uint64_t)f << (L0 + 1);
-    const uint32_t L = L0 + ((a * a <= 2ull * F * F) ? 1u : 0u);
-    return max(1u, min((uint32_t)maxbits, L));
-}
+// priority-queue Huffman; its cost against an optimal length-limited code is tabulated in
+// DESIGN.md.  init_len and fit_classes (steps 2-4) live in huff_fit.h, shared with the CPU test.
 
 // the same for at most 64 symbols (precode, distance code): one key per lane, 64-key sort
 __device__ void wave_build_lengths64(const uint32_t* freq, int nsym, int maxbits, uint8_t* lens) {
@@ -365,33 +311,7 @@ __device__ __forceinline__ uint32_t fixed_lit_code(uint32_t s) {
     return bitrev(c, fixed_lit_len(s));
 }
 
-// RLE plan of one run of code lengths (v, r): zero runs use 18/17, others v then 16s.
-// Never a 16 after a 17/18, and sequences never span HLIT/HDIST (the reference
-// inflate decodes the two sequences separately, inflate.hpp:216-220, and repeats the last
-// *literal* length on 16, inflate.hpp:181).
-struct RunPlan {
-    uint32_t n18, last18, n17, r17, nlit, n16, last16;  // last18/last16: length of final repeat
-};
-__device__ __forceinline__ RunPlan plan_run(uint32_t v, uint32_t r) {
-    RunPlan p = {0, 0, 0, 0, 0, 0, 0};
-    if (v == 0) {
-        p.n18 = r / 138;
-        p.last18 = 138;
-        uint32_t rem = r % 138;
-        if (rem >= 11) { p.n18++; p.last18 = rem; }
-        else if (rem >= 3) { p.n17 = 1; p.r17 = rem; }
-        else p.nlit = rem;
-    } else {
-        uint32_t q = r - 1;
-        p.nlit = 1;
-        p.n16 = q / 6;
-        p.last16 = 6;
-        uint32_t rem = q % 6;
-        if (rem >= 3) { p.n16++; p.last16 = rem; }
-        else p.nlit += rem;
-    }
-    return p;
-}
+// (the RLE plan of one run of code lengths, plan_run / RunPlan: huff_fit.h)
 
 // ---------------------------------------------------------------------------------------
 // the segment kernel: 1024 threads (16 waves) per segment, one workgroup per CU
@@ -1602,7 +1522,7 @@ __device__ EmCodes em_build_codes(EmWave& W) {
         const uint32_t f = em_valid(c, lane) ? W.freq[em_slot(c, lane)] : 0u;
         const uint32_t F = c < 5 ? Fl : Fd;
         const uint32_t L0 = init_len(f, F, c < 5 ? DF_LIT_MAXBITS : DF_DIST_MAXBITS);
-        const uint32_t k0 = L0 ? 2 * L0 + (((uint64_t)f << L0) <= F ? 1u : 0u) : 0u;
+        const uint32_t k0 = L0 ? 2 * L0 + init_half(f, F, L0) : 0u;
         uint32_t mine = 0, w0 = 0;
 #pragma unroll
         for (int k = 2; k <= 2 * DF_LIT_MAXBITS + 1; k++) {
@@ -1934,7 +1854,7 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
             W.rk[64 * c + lane] = (uint16_t)rl;
         }
         wave_sync();
-        wave_build_lengths64(W.prefreq, 19, 7, W.prelen);
+        wave_build_lengths64(W.prefreq, 19, DF_PRE_MAXBITS, W.prelen);
         wave_sync();
         wave_assign_codes(W.prelen, 19, W.precode);
         wave_sync();
