@@ -9,10 +9,12 @@
 //   1. each lane reads its block header (BTYPE; stored segments are handled right there);
 //   2. each lane builds its dynamic segment's precode table (ln_lane_pretab);
 //   3. each lane decodes its code-length sequence once into bytes (branch-free steps);
-//   4. each lane builds its segment's 9-bit lit/len and 6-bit distance tables (ln_lane_table);
+//   4. each segment's 9-bit lit/len and 6-bit distance tables are built by a lane pair, its own
+//      lane and the one 32 above (ln_pair_tables);
 //   5. each lane decodes its tokens: a 64-bit window per symbol from a per-lane LDS ring of
-//      the stream (no refill branch), table lookups, select-based token logic.  The decoded
-//      tokens go to HBM as 32-bit words:
+//      the stream (no refill branch), table lookups, select-based token logic; while a lane of
+//      the wave is inside a long run, a step takes up to four equal matches at once.  The
+//      decoded tokens go to HBM as 32-bit words:
 //     match        1 | L(16) | d-1(15)          consecutive matches with the same distance are
 //                                               merged: one periodic copy of their summed length
 //     literal run  0 | count(7) = 1..3 | bytes(24)
@@ -37,6 +39,7 @@
 #include "dmx_device.h"
 #include "dmx_internal.h"
 #include "inflate_common.h"
+#include <type_traits>
 
 namespace dmx {
 
@@ -63,8 +66,9 @@ typedef uint16_t u16_unaligned __attribute__((aligned(1)));
 static_assert(LN_HDR_QUADS * 16 <= LN_LENS, "header quads overlap the code lengths");
 // segments per 64-thread workgroup: 32 x 1280 B = 40 KiB of LDS, four workgroups per CU, one
 // decoding wave per SIMD holding 32 segments.  The branch-free token step is VALU-issue-bound,
-// so one wave of 32 segments beats two of 16 (1 GiB text inflate 12.3 -> 10.9 ms); the
-// table builds take the other half of the wave's lanes.
+// so one wave of 32 segments beats two of 16 (1 GiB text inflate 12.3 -> 10.9 ms).  Lanes
+// 32..63 hold no segment: they work only in the lit/len and distance table builds, where lane
+// s + 32 takes half of segment s's work (ln_pair_tables), and in the wave-wide loads.
 constexpr uint32_t LN_LANES = 32;
 // resolve workgroup: RS_NT threads around one window.  Wave 0 runs the token steps, the
 // workgroup fills periodic copies of >= RS_BIG bytes (repeat, zeros, image rows: segments of at
@@ -104,8 +108,8 @@ __device__ __forceinline__ uint32_t ln_lit_entry(uint32_t s, uint32_t l) {
     return (l << 11) | s;
 }
 
-// Per-lane canonical tables (one lane per segment, all segments of the wave at once).  Nine 9-bit
-// counters or next codes per lane in two registers: code lengths 1..6 in lo, 7..9 in hi.
+// Canonical tables (all segments of the wave at once).  Nine 9-bit counters or next codes per
+// lane in two registers: code lengths 1..6 in lo, 7..9 in hi.
 struct Pk9 {
     uint64_t lo;
     uint32_t hi;
@@ -117,21 +121,15 @@ __device__ __forceinline__ void pk_add(Pk9& p, uint32_t L) {  // L in 0..9 (0: n
     p.lo += (L - 1u) < 6u ? 1ull << (9 * (L - 1)) : 0ull;
     p.hi += L >= 7 ? 1u << (9 * (L - 7)) : 0u;
 }
-// The table T[0, 2^B) of a code with per-length counts `cnt` (lengths <= B), symbols s < nsym of
-// lengths nib(s) (4-bit nibbles, packed 8 per word: word(k) holds symbols 8k .. 8k + 7); entries
-// ent(s, L) whose length field is (e >> lsh) & lmask.  RFC 1951 3.2.2 canonical codes: the next
-// code of each length, symbols in order.  Each symbol's entry goes to its bit-reversed code
-// (a "seed", below 2^L); the table is then completed level by level: for b = 1 .. B-1 every entry
-// in [0, 2^b) of length <= b is copied to + 2^b (a longer code's seed stays, and its own positions
-// come from its seed).  Entries not yet written hold `mark` (a length above B).  Index rotation
-// by lane keeps the lanes' accesses (regions 1152 B apart) off a common bank.  B >= 6.  Returns false
-// unless the code is complete.
-template <int B, int NL, class Word, class Ent>
-__device__ __forceinline__ bool ln_lane_table(uint16_t* T, const Pk9& cnt, uint32_t nsym, Word word, Ent ent,
-                                              uint32_t lsh, uint32_t lmask, uint32_t mark) {
-    const uint32_t lane = lane_id();
+__device__ __forceinline__ Pk9 pk_sum(const Pk9& a, const Pk9& b) {  // (fields stay below 512)
+    return Pk9{a.lo + b.lo, a.hi + b.hi};
+}
+// RFC 1951 3.2.2: the first code of each length 1..B of a code with per-length counts `cnt`, into
+// nc; returns the Kraft sum in units of 2^-B (2^B: the code is complete).
+template <int B>
+__device__ __forceinline__ uint32_t ln_first_codes(const Pk9& cnt, Pk9& nc) {
     uint32_t kraft = 0, code = 0;
-    Pk9 nc = {0ull, 0u};
+    nc = Pk9{0ull, 0u};
 #pragma unroll
     for (uint32_t l = 1; l <= (uint32_t)B; l++) {
         const uint32_t c = pk_get(cnt, l);
@@ -140,46 +138,38 @@ __device__ __forceinline__ bool ln_lane_table(uint16_t* T, const Pk9& cnt, uint3
         if (l <= 6) nc.lo |= (uint64_t)code << (9 * (l - 1));
         else nc.hi |= code << (9 * (l - 7));
     }
-    if (kraft != (1u << B)) return false;
-    constexpr uint32_t NW = (1u << B) / 2;  // table words
-    uint64_t* const T64w = reinterpret_cast<uint64_t*>(T);
-    const uint64_t m4 = (uint64_t)(mark | (mark << 16)) * 0x0000000100000001ull;
-#pragma unroll 4
-    for (uint32_t w = 0; w < NW / 2; w++) T64w[(w + lane) & (NW / 2 - 1)] = m4;
-    // symbols below NL (a multiple of 8, < nsym): entry (L << lsh) | sym, no bound test
-    // (each word read one iteration ahead, its LDS latency behind the 8 symbols)
-    uint32_t xn = word(0);
-    for (uint32_t k = 0; 8 * k < (uint32_t)NL; k++) {
-        const uint32_t x = xn;
-        xn = word(k + 1);  // (k + 1 <= NL / 8: the next loop's first word)
+    return kraft;
+}
+// 8 symbols of a code (their lengths as nibbles of x, symbols sym0 .. sym0 + 7): each symbol's
+// entry ent(sym, L) goes to its bit-reversed code (its "seed", below 2^L); nc holds the next code
+// of each length.
+template <class Ent>
+__device__ __forceinline__ void ln_seeds8(uint16_t* T, Pk9& nc, uint32_t x, uint32_t sym0, Ent ent) {
 #pragma unroll
-        for (uint32_t i = 0; i < 8; i++) {
-            const uint32_t sym = 8 * k + i, L = (x >> (4 * i)) & 15u;
-            if (L != 0u) {
-                const uint32_t c = pk_get(nc, L);
-                T[__builtin_bitreverse32(c) >> (32 - L)] = (uint16_t)((L << lsh) | sym);
-            }
-            pk_add(nc, L);
+    for (uint32_t i = 0; i < 8; i++) {
+        const uint32_t L = (x >> (4 * i)) & 15u;
+        if (L != 0u) {
+            const uint32_t c = pk_get(nc, L);
+            T[__builtin_bitreverse32(c) >> (32 - L)] = (uint16_t)ent(sym0 + i, L);
         }
+        pk_add(nc, L);
     }
-    for (uint32_t k = NL / 8; 8 * k < nsym; k++) {
-        const uint32_t x = k == NL / 8 && NL > 0 ? xn : word(k);
-#pragma unroll
-        for (uint32_t i = 0; i < 8; i++) {
-            const uint32_t sym = 8 * k + i, L = (x >> (4 * i)) & 15u;
-            if (L != 0u && sym < nsym) {
-                const uint32_t c = pk_get(nc, L);
-                T[__builtin_bitreverse32(c) >> (32 - L)] = (uint16_t)ent(sym, L);
-            }
-            pk_add(nc, L);
-        }
-    }
+}
+// A table T[0, 2^B) whose seeds are written (every other entry holds a mark: a length above B) is
+// completed level by level: for b = 1 .. B-1 every entry in [0, 2^b) of length <= b (length
+// field (e >> lsh) & lmask) is copied to + 2^b; a longer code's seed stays, and its own
+// positions come from its seed.  The two lanes of a pair (hi: the upper one, own: the lane
+// modulo 32) halve the index range of each level from 4 on; below that both write the same
+// values.  Reads lie in [0, n) and writes in [n, 2n), and the next level reads what both lanes
+// wrote: wave_sync() between levels.  Index rotation by `own` keeps the wave's segments
+// (regions 1152 B apart) off a common bank.  B >= 6.
+template <int B>
+__device__ __forceinline__ void ln_pair_levels(uint16_t* T, uint32_t lsh, uint32_t lmask, bool hi, uint32_t own) {
     auto put = [&](uint32_t q, uint32_t e, uint32_t b) {
         if (((e >> lsh) & lmask) <= b) T[q] = (uint16_t)e;
     };
     // levels 1 and 2 entry by entry; from level 3 on (n >= 8) the reads of a batch go first (8
-    // entries as two 8-byte reads, 4-entry aligned, rotated by 4 * lane), then the writes
-    // (reads in [0, n), writes in [n, 2n): no overlap)
+    // entries as two 8-byte reads, 4-entry aligned, rotated by 4 * own), then the writes
     put(2, T[0], 1);
     put(3, T[1], 1);
 #pragma unroll
@@ -188,8 +178,10 @@ __device__ __forceinline__ bool ln_lane_table(uint16_t* T, const Pk9& cnt, uint3
 #pragma unroll
     for (uint32_t b = 3; b < (uint32_t)B; b++) {
         const uint32_t n = 1u << b;
-        for (uint32_t i = 0; i < n; i += 8) {
-            const uint32_t q0 = (i + 4 * lane) & (n - 1), q1 = (q0 + 4) & (n - 1);
+        const uint32_t part = b == 3 ? n : n / 2;  // entries per lane
+        const uint32_t from = (b != 3 && hi) ? n / 2 : 0u;
+        for (uint32_t i = 0; i < part; i += 8) {
+            const uint32_t q0 = (from + i + 4 * own) & (n - 1), q1 = (q0 + 4) & (n - 1);
             const uint64_t v0 = T64[q0 >> 2], v1 = T64[q1 >> 2];
 #pragma unroll
             for (uint32_t k = 0; k < 4; k++) {
@@ -197,13 +189,115 @@ __device__ __forceinline__ bool ln_lane_table(uint16_t* T, const Pk9& cnt, uint3
                 put(q1 + n + k, (uint32_t)(v1 >> (16 * k)) & 0xFFFFu, b);
             }
         }
+        wave_sync();
     }
+}
+// The fixed code's lengths (RFC 1951 3.2.6) as packed nibbles, word k: 8 (0..143), 9 (144..255),
+// 7 (256..279), 8 (280..287), distance 5
+__device__ __forceinline__ uint32_t ln_fixed_word(uint32_t k) {
+    return k < 18 ? 0x88888888u : k < 32 ? 0x99999999u : k < 35 ? 0x77777777u : k < 36 ? 0x88888888u : 0x55555555u;
+}
+
+// The 9-bit lit/len table (R + 0, 512 x u16) and the 6-bit distance table (R + LN_DIST, 64 x u16)
+// of one segment, built by a LANE PAIR: lane s (the segment's owner) and lane s + 32 (hi), both
+// with the segment's region R and shared words PK, all pairs of the wave at once.  Code lengths:
+// one byte per symbol at R + LN_LENS (lit/len 0..287, distance 288..319), or the fixed code.
+//   1. The lengths are packed to nibbles, 8 symbols per word, words 0..39 (0..35 lit/len, 36..39
+//      distance): the owner packs and counts words 0..19, hi words 20..39.  Words below 32 go to
+//      PK (rotated by the lane: bank spread), words 32..39 to the distance-table area, because
+//      the lit/len table overwrites the length bytes.  The pair exchanges its per-length counts.
+//   2. Both lanes make the Kraft test of both codes from the same totals (so both return the
+//      same), then mark their half of each table.
+//   3. Canonical seeds (ln_seeds8): the owner takes lit/len symbols 0..159 (words 0..19), hi
+//      160..287 and then the 32 distance symbols -- 160 symbols each, the words each lane packed
+//      itself.  hi starts from next codes advanced by the owner's counts.
+//   4. Level doubling, each level's index range halved (ln_pair_levels).
+// The tables are those a single lane builds symbol by symbol: the seeds are the same entries at
+// the same places, and a level reads only what earlier levels (or the seeds) completed.
+// Returns false unless both codes are complete.
+__device__ __forceinline__ bool ln_pair_tables(uint8_t* R, uint32_t* PK, bool fixed) {
+    const uint32_t lane = lane_id(), own = lane & 31u;
+    const bool hi = lane >= 32u;
+    uint32_t* const PD = reinterpret_cast<uint32_t*>(R + LN_DIST);
+    const uint32_t* const LW = reinterpret_cast<const uint32_t*>(R + LN_LENS);
+    uint16_t* const lt = reinterpret_cast<uint16_t*>(R);
+    uint16_t* const dt = reinterpret_cast<uint16_t*>(R + LN_DIST);
+    const uint32_t k0 = hi ? 20u : 0u;
+    // ca: counts of this lane's words 0..15 (lit/len on both lanes); cb: of its words 16..19 (the
+    // owner's lit/len symbols 128..159, hi's distance code)
+    Pk9 ca = {0ull, 0u}, cb = {0ull, 0u};
+    auto pack = [&](uint32_t i, Pk9& cnt) {
+        const uint32_t k = k0 + i;
+        const uint32_t lo = LW[2 * k], hw = LW[2 * k + 1];  // 8 length bytes (each <= 9)
+        auto nib4 = [](uint32_t x) {
+            return (x & 0xFu) | ((x >> 4) & 0xF0u) | ((x >> 8) & 0xF00u) | ((x >> 12) & 0xF000u);
+        };
+        const uint32_t x = fixed ? ln_fixed_word(k) : nib4(lo) | (nib4(hw) << 16);
+        *(k < 32 ? PK + ((k + own) & 31) : PD + (k - 32)) = x;
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) pk_add(cnt, (x >> (4 * j)) & 15u);
+    };
+#pragma unroll 4
+    for (uint32_t i = 0; i < 16; i++) pack(i, ca);
+#pragma unroll 4
+    for (uint32_t i = 16; i < 20; i++) pack(i, cb);
+    wave_sync();  // (the marks below overwrite length bytes the other lane packed)
+    const Pk9 oa = {__shfl_xor(ca.lo, 32), __shfl_xor(ca.hi, 32)};
+    const Pk9 ob = {__shfl_xor(cb.lo, 32), __shfl_xor(cb.hi, 32)};
+    const Pk9 low = hi ? pk_sum(oa, ob) : pk_sum(ca, cb);  // lit/len symbols 0..159
+    const Pk9 cl = pk_sum(low, hi ? ca : oa);
+    const Pk9 cd = hi ? cb : ob;
+    Pk9 ncl, ncd;
+    const uint32_t kl = ln_first_codes<9>(cl, ncl), kd = ln_first_codes<6>(cd, ncd);
+    if (kl != 512u || kd != 64u) return false;
+    if (hi) ncl = pk_sum(ncl, low);
+    // words 32..39 (hi's own) leave the distance-table area before the marks
+    uint32_t p[8];
+#pragma unroll
+    for (uint32_t i = 0; i < 8; i++) p[i] = PD[i];
+    wave_sync();
+    uint64_t* const L64 = reinterpret_cast<uint64_t*>(R);
+    uint64_t* const D64 = reinterpret_cast<uint64_t*>(R + LN_DIST);
+    const uint64_t ml = 0x7800780078007800ull, md = 0x8700870087008700ull;  // lengths 15 and 7
+#pragma unroll 4
+    for (uint32_t w = 0; w < 64; w++) L64[(hi ? 64u : 0u) + ((w + own) & 63u)] = ml;
+#pragma unroll
+    for (uint32_t w = 0; w < 8; w++) D64[(hi ? 8u : 0u) + ((w + own) & 7u)] = md;
+    wave_sync();
+    // seeds.  Words 0..11 of each lane: symbols below 256, entry (L << 11) | sym (each word read
+    // one iteration ahead, its LDS latency behind the 8 symbols)
+    auto plain = [](uint32_t sym, uint32_t L) { return (L << 11) | sym; };
+    uint32_t xn = PK[(k0 + own) & 31];
+    for (uint32_t i = 0; i < 12; i++) {
+        const uint32_t x = xn;
+        xn = PK[(k0 + i + 1 + own) & 31];  // (hi, i = 11: not used)
+        ln_seeds8(lt, ncl, x, 8 * (k0 + i), plain);
+    }
+    // words 12..15: the owner's symbols 96..127, hi's 256..287 (ln_lit_entry serves both)
+#pragma unroll
+    for (uint32_t i = 12; i < 16; i++) {
+        const uint32_t x = hi ? p[i - 12] : (i == 12 ? xn : PK[(i + own) & 31]);
+        ln_seeds8(lt, ncl, x, 8 * (k0 + i), [](uint32_t sym, uint32_t L) { return ln_lit_entry(sym, L); });
+    }
+    // words 16..19: the owner's symbols 128..159; hi's distance symbols 0..31, entry
+    // 1 | L << 8 | sym in the distance table
+    uint16_t* const T = hi ? dt : lt;
+    Pk9 nc = hi ? ncd : ncl;
+#pragma unroll
+    for (uint32_t i = 16; i < 20; i++) {
+        const uint32_t x = hi ? p[i - 12] : PK[(i + own) & 31];
+        ln_seeds8(T, nc, x, hi ? 8 * (i - 16) : 8 * i,
+                  [&](uint32_t sym, uint32_t L) { return hi ? 0x8000u | (L << 8) | sym : (L << 11) | sym; });
+    }
+    wave_sync();
+    ln_pair_levels<9>(lt, 11, 15, hi, own);
+    ln_pair_levels<6>(dt, 8, 7, hi, own);
     return true;
 }
 
 // The precode table of one segment per lane: T[0, 128) as u8 entries sym | len << 5 for the
 // 19 precode lengths pl (3 bits each, by symbol), by the same canonical seeds and level doubling
-// as ln_lane_table (per-length counts and next codes packed in registers; from level 3 on the
+// as ln_pair_tables (per-length counts and next codes packed in registers; from level 3 on the
 // doubling moves 8 entries per 8-byte word, the entries to copy picked by a per-byte compare of
 // their length fields).  0xFF marks an entry not yet written.  False unless the code is complete.
 __device__ __forceinline__ bool ln_lane_pretab(uint8_t* T, uint64_t pl) {
@@ -499,44 +593,15 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
     }
     if (dbg) dbg[2] = __builtin_amdgcn_s_memtime();
 
-    // ---- lit/len (9-bit) and distance (6-bit) tables, one lane per segment (ln_lane_table) -----
-    // The code lengths are first packed to nibbles (symbols 0..255 into the lane's 128 B of the
-    // shared area, 256..287 and the distance lengths into its distance-table area), because the
-    // lit/len table overwrites their bytes [LN_LENS, 1024); the distance table is built last.
-    if (huff && !flags) {
-        const bool fixed = btype == 1;
-        uint32_t* const PK = reinterpret_cast<uint32_t*>(SH + lane * LN_PRE_BYTES);  // words 0..31
-        uint32_t* const PD = reinterpret_cast<uint32_t*>(R + LN_DIST);             // words 32..39
-        const uint32_t* const LW = reinterpret_cast<const uint32_t*>(R + LN_LENS);
-        Pk9 cl = {0ull, 0u}, cd = {0ull, 0u};
-#pragma unroll 8
-        for (uint32_t k = 0; k < 40; k++) {
-            // fixed code (RFC 1951 3.2.6): 8 (0..143), 9 (144..255), 7 (256..279), 8 (280..287), 5
-            const uint32_t fw = k < 18 ? 0x88888888u : k < 32 ? 0x99999999u : k < 35 ? 0x77777777u
-                              : k < 36 ? 0x88888888u : 0x55555555u;
-            const uint32_t lo = LW[2 * k], hi = LW[2 * k + 1];  // 8 length bytes (each <= 9)
-            auto nib4 = [](uint32_t x) {
-                return (x & 0xFu) | ((x >> 4) & 0xF0u) | ((x >> 8) & 0xF00u) | ((x >> 12) & 0xF000u);
-            };
-            const uint32_t x = fixed ? fw : nib4(lo) | (nib4(hi) << 16);
-            if (k < 32) PK[(k + lane) & 31] = x;  // rotated by lane (bank spread), read back alike
-            else PD[k - 32] = x;
-#pragma unroll
-            for (uint32_t i = 0; i < 8; i++) {
-                if (k < 36) pk_add(cl, (x >> (4 * i)) & 15u);
-                else pk_add(cd, (x >> (4 * i)) & 15u);
-            }
-        }
-        const uint32_t dw0 = PD[4], dw1 = PD[5], dw2 = PD[6], dw3 = PD[7];
-        uint16_t* const lt = reinterpret_cast<uint16_t*>(R);
-        uint16_t* const dt = reinterpret_cast<uint16_t*>(R + LN_DIST);
-        bool ok = ln_lane_table<9, 256>(
-            lt, cl, 288u, [&](uint32_t k) { return k < 32 ? PK[(k + lane) & 31] : PD[k - 32]; },
-            [](uint32_t sym, uint32_t len) { return ln_lit_entry(sym, len); }, 11, 15, 0x7800u);
-        ok = ok && ln_lane_table<6, 0>(
-            dt, cd, 32u, [&](uint32_t k) { return k == 0 ? dw0 : k == 1 ? dw1 : k == 2 ? dw2 : dw3; },
-            [](uint32_t sym, uint32_t len) { return 0x8000u | (len << 8) | sym; }, 8, 7, 0x8700u);
-        if (!ok) flags |= SEGF_EXOTIC;
+    // ---- lit/len (9-bit) and distance (6-bit) tables: lane s + 32 helps lane s (ln_pair_tables),
+    //      active exactly when its owner decodes a Huffman segment ---------------------------------
+    {
+        static_assert(NL == 32, "a lane pair per segment: 64 lanes, 32 segments");
+        const uint32_t own = lane & (LN_LANES - 1);
+        const bool build = __shfl((int)(huff && !flags), (int)own) != 0;
+        const bool fixed = __shfl((int)(btype == 1), (int)own) != 0;
+        if (build && !ln_pair_tables(lds + own * LN_REGION, reinterpret_cast<uint32_t*>(SH + own * LN_PRE_BYTES), fixed))
+            flags |= SEGF_EXOTIC;
     }
     wave_sync();
     if (dbg) dbg[3] = __builtin_amdgcn_s_memtime();
@@ -550,11 +615,15 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
         // bits) -- decodes from one window with no refill branch.  Every LN_PERIOD steps the
         // lane loads the next quad of its stream into a staging register and writes the quad
         // staged two periods earlier into the ring (loads complete off the critical path); a
-        // quad goes into the ring only once the one it replaces is consumed.  LN_PERIOD steps
-        // consume <= 99 bits < one quad, so the ring stays >= 5 quads ahead.  The token logic
-        // is written with selects so the lanes of a wave, each on its own segment, execute
-        // one short path per step.
+        // quad goes into the ring only once the one it replaces is consumed.  A step consumes
+        // <= LN_STEP_BITS = 42 bits (one symbol <= 33; a folded run of equal matches is capped
+        // at floor(127 / LN_PERIOD)), so LN_PERIOD steps consume <= 126 bits < one quad and the
+        // ring stays >= 5 quads ahead.  The token logic is written with selects so the lanes
+        // of a wave, each on its own segment, execute one short path per step.
         constexpr uint32_t LN_PERIOD = 3;
+        constexpr uint32_t LN_STEP_BITS = 127 / LN_PERIOD;
+        constexpr uint32_t LN_FOLD_MAX = 4;  // equal matches one step takes
+        static_assert(LN_STEP_BITS >= 33 && LN_STEP_BITS < 64, "one symbol fits; the window funnel takes 1..63");
         u32x4* const ring = reinterpret_cast<u32x4*>(SH + lane * LN_PRE_BYTES);
         const uint64_t* const ring2 = reinterpret_cast<const uint64_t*>(ring);
         uint32_t bp = br.bitpos();
@@ -588,7 +657,8 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             const uint32_t pr = bp >> 6;
             win = window_at(bp, ring2[pr & 15], ring2[(pr + 1) & 15]);
         }
-        auto step = [&]() -> bool {
+        auto step = [&](auto folds) __attribute__((always_inline)) -> bool {
+            constexpr bool FOLD = decltype(folds)::value && !SPLIT;
             const uint32_t pr = bp >> 6;
             const uint64_t nq0 = ring2[(pr + 1) & 15], nq1 = ring2[(pr + 2) & 15];
             // lit/len symbol, then the distance decoded from the same window (used for lengths)
@@ -610,7 +680,35 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             const uint32_t sym2 = de & 511, cl2 = (de >> 11) & 15;
             const bool lit2 = !isl & (sym < 256) & ((de & 0x8000u) == 0u) & (sym2 < 256) &
                               (outpos + 2 <= CAP) & (!SPLIT | (outpos + 1 != HALF));
-            const uint32_t c = n1 + (isl ? dcl + dx : (lit2 ? cl2 : 0u));  // 1 .. 33 bits
+            const uint32_t c1 = n1 + (isl ? dcl + dx : (lit2 ? cl2 : 0u));  // 1 .. 33 bits
+            // Run fold (not with SPLIT: no word may merge across HALF).  A long run reaches the
+            // decoder as equal matches (L, d) back to back, because LEN stops at 258: the window
+            // then holds the same c1 bits several times over.  When this symbol is a match that
+            // will be accepted, the step takes nf copies of it at once: as many as stand whole
+            // in the window (the first tz bits of win ^ (win >> c1) are zero exactly when the
+            // window repeats with period c1 that far), at most LN_FOLD_MAX, within
+            // LN_STEP_BITS bits, and with outpos + nf L <= CAP.  Decoding is a function of the
+            // bits and the tables alone, so symbol by symbol those bits give nf - 1 more matches
+            // (L, d); each is accepted (d <= outpos holds after the first, the same distance
+            // symbol raises no flag, the CAP test is made here) and each continues the pending
+            // word (mcont: pa <= outpos, so pa + nf L <= CAP fits the 16-bit length).  The token
+            // words, ntok, outpos, the final bp and the flags are therefore those of nf steps,
+            // also where copies lie beyond the end-of-block or the stream end: the symbol-wise
+            // decoder reads the same bits there.  Any limit not met: nf = 1, the plain step.
+            uint32_t nf = 1;
+            if (FOLD) {
+                static_assert(SPLIT || CAP <= 0xFFFFu, "a folded match must fit the length field");
+                const uint64_t rep = win ^ (win >> c1);
+                const uint32_t tz = (uint32_t)__builtin_ctzll(rep | (1ull << 63));
+                const uint32_t span = min(tz, LN_STEP_BITS - c1);  // bits further copies may take
+                const uint32_t room = CAP - outpos;
+                const bool m0 = isl & (ds < 30u) & (d <= outpos);
+#pragma unroll
+                for (uint32_t k = 2; k <= LN_FOLD_MAX; k++)
+                    nf += (m0 & ((k - 1) * c1 <= span) & (k * L <= room)) ? 1u : 0u;
+            }
+            const uint32_t c = nf * c1;    // <= LN_STEP_BITS when folded
+            const uint32_t Lf = nf * L;    // the match handed to the token logic
             const uint64_t ext = window_at(bp + 64, nq0, nq1);
             win = (win >> c) | ((ext << 1) << (63 - c));
             bp += c;
@@ -648,8 +746,8 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             const bool emit = prod & !cont & (pk != 0u);
             const uint32_t ew = lsplit ? (3u << 24) | pa | (sym << 16)
                               : pk == 1u ? (pd << 24) | pa : 0x80000000u | (pa << 15) | (pd - 1u);
-            const uint32_t a_cont = lcont ? (pa | (lb << (8 * pd))) : (pa + L);
-            const uint32_t a_new = lsplit ? sym2 : lt ? lb : L;
+            const uint32_t a_cont = lcont ? (pa | (lb << (8 * pd))) : (pa + Lf);
+            const uint32_t a_new = lsplit ? sym2 : lt ? lb : Lf;
             const uint32_t d_cont = lcont ? pd + nl : pd;
             const uint32_t d_new = lsplit ? 1u : lt ? nl : d;
             const uint32_t npa = cont ? a_cont : a_new;
@@ -657,7 +755,7 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             pa = prod ? npa : pa;
             pd = prod ? npd : pd;
             pk = prod ? (lt ? 1u : 2u) : pk;
-            outpos += prod ? (lt ? nl : L) : 0u;
+            outpos += prod ? (lt ? nl : Lf) : 0u;
             // queue of 4 token words (shift register), one 16-byte store per 4 words
             q0 = emit ? q1 : q0;
             q1 = emit ? q2 : q1;
@@ -683,11 +781,48 @@ __global__ __launch_bounds__(64) void k_inflate_lanes(InflateArgs A, LaneArgs B)
             nextq += adv ? 1u : 0u;
         };
         static_assert(LN_PERIOD == 3, "steps per period below");
-        for (;;) {
-            stage(S0, v0, tq0);
-            if (!step() || !step() || !step()) break;
-            stage(S1, v1, tq1);
-            if (!step() || !step() || !step()) break;
+        // The fold's tests cost every step about a tenth more, which text-like data never earns
+        // back (1 GiB text inflate 8.7 -> 9.4 ms with the fold in every step), so the steps come
+        // in two forms, each in a loop of its own, and the wave changes to the folding loop only
+        // while some lane is inside a run: its pending match is longer than two whole matches
+        // (looked at once per trip).  Two loops and not two forms inside one: where the forms
+        // join, the compiler copies the loop's registers -- the staging registers among them,
+        // and that copy waits for the load -- which cost text 2 %.
+        constexpr std::false_type PLAIN{};
+        constexpr std::true_type FOLDING{};
+        auto in_run = [&]() -> bool { return !SPLIT && __ballot((pk == 2u) & (pa > 2u * 258u)) != 0; };
+        bool go = true, runs = false;
+        if constexpr (SPLIT) {  // no fold: one loop (as two, the second one dead, C4 inflate read 1.4 % longer)
+            for (;;) {
+                stage(S0, v0, tq0);
+                if (!step(PLAIN) || !step(PLAIN) || !step(PLAIN)) break;
+                stage(S1, v1, tq1);
+                if (!step(PLAIN) || !step(PLAIN) || !step(PLAIN)) break;
+            }
+            go = false;
+        }
+        while (go) {
+            if (!runs) {
+                do {
+                    stage(S0, v0, tq0);
+                    go = step(PLAIN) && step(PLAIN) && step(PLAIN);
+                    if (go) {
+                        stage(S1, v1, tq1);
+                        go = step(PLAIN) && step(PLAIN) && step(PLAIN);
+                    }
+                    runs = in_run();
+                } while (go && !runs);
+            } else {
+                do {
+                    stage(S0, v0, tq0);
+                    go = step(FOLDING) && step(FOLDING) && step(FOLDING);
+                    if (go) {
+                        stage(S1, v1, tq1);
+                        go = step(FOLDING) && step(FOLDING) && step(FOLDING);
+                    }
+                    runs = in_run();
+                } while (go && runs);
+            }
         }
         endbit = bp;
         if (dbg) dbg[4] = __builtin_amdgcn_s_memtime();
