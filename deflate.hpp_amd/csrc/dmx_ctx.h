@@ -93,6 +93,11 @@ struct dmx_ctx {
     // the chain scratch (tile counts, candidates, jump tables, member table); descriptors + results
     // (bgzt: the candidate scan's tile counts and offsets, which outlive the sizing of bgzc)
     DevBuf bgzs, bgzc, bgzd, bgzt;
+    // seek index: the ranged read's head + spans, or the window gather's slot list; and, for the
+    // one call that asks for an index (dmx_inflate_index_device, null otherwise), where the path
+    // that decodes the stream lists its checkpoints
+    DevBuf seekd;
+    dmx::SeekTap* seek_tap = nullptr;
     dmx::HostRes* hres = nullptr;      // host address (nullptr: not available, results are copied)
     dmx::HostRes* hres_dev = nullptr;  // the same block as the device sees it
     dmx::SpecKnob spec = dmx::SpecKnob::On;  // DMX_INFLATE_SPEC, read at dmx_create

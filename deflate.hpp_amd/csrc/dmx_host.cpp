@@ -949,7 +949,8 @@ void dmx_destroy(dmx_ctx* c) {
                       &c->ltokoff, &c->lntok, &c->lcaps, &c->lheavy, &c->rtmp, &c->rchain, &c->fbc, &c->fbh, &c->fbo, &c->fbl,
                       &c->fbs, &c->fbt, &c->fbk, &c->fbu, &c->fbch, &c->fbco, &c->fbcs, &c->fbimg, &c->fbstop, &c->fbwin, &c->fbopen, &c->fbvm, &c->fbvh,
                       &c->fbreg, &c->fbJ, &c->fbvis, &c->fbph,
-                      &c->ck, &c->btab, &c->bres, &c->adf, &c->ainf, &c->fdesc, &c->bgzs, &c->bgzc, &c->bgzd, &c->bgzt})
+                      &c->ck, &c->btab, &c->bres, &c->adf, &c->ainf, &c->fdesc, &c->bgzs, &c->bgzc, &c->bgzd, &c->bgzt,
+                      &c->seekd})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1726,6 +1727,87 @@ int dmx_inflate_bgzf_range_device(dmx_ctx* c, const void* d_in, size_t n, const 
             return launch_bgzf_range_desc(in, d_idx, count, u0, u1, out, edge, b.desc, b.order, st);
         },
         [&] { return launch_bgzf_range_copy(d_idx, count, u0, u1, edge, out, st); });
+    c->stats.out_bytes = rc == DMX_OK ? len : 0;
+    return rc;
+}
+
+// ---- seek index and ranged reads for unblocked streams ----------------------------------------
+// (the decisions: seek_plan.h; the kernels: inflate_span.hip; the checkpoint hand-over: the
+// context's seek_tap, which host_fb.cpp and host_inflate.cpp fill when it is set)
+size_t dmx_seek_windows_bound(size_t cap, size_t spacing) {
+    return spacing < DMX_SEEK_WINDOW ? 0 : (cap / spacing + 2) * (size_t)DMX_SEEK_WINDOW;
+}
+
+int dmx_inflate_index_device(dmx_ctx* c, const void* d_in, size_t n, void* d_out, size_t cap, size_t spacing,
+                             dmx_seek_entry* entries, size_t entry_cap, void* d_windows, size_t windows_cap,
+                             size_t* count, size_t* out_len, void* stream) {
+    if (!c || (!d_in && n) || !d_out || !out_len || !count || spacing < DMX_SEEK_WINDOW ||
+        (!entries && entry_cap) || (!d_windows && windows_cap))
+        return DMX_ERR_ARG;
+    *count = 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    SeekTap tap;
+    c->seek_tap = &tap;
+    const int rc = inflate_device_locked(c, (const uint8_t*)d_in, n, (uint8_t*)d_out, cap, out_len, nullptr, st);
+    c->seek_tap = nullptr;
+    if (rc != DMX_OK) return rc;
+    const std::vector<dmx_seek_entry> sel = seek_select(tap.cands.data(), tap.cands.size(), spacing);
+    *count = sel.size();
+    if (entry_cap < sel.size() + 1 || windows_cap / DMX_SEEK_WINDOW < sel.size()) return DMX_ERR_CAPACITY;
+    std::copy(sel.begin(), sel.end(), entries);
+    entries[sel.size()] = dmx_seek_entry{8 * c->last_end, *out_len, 0, 0};
+    std::vector<SeekSlot> slots;
+    for (size_t k = 0; k < sel.size(); k++)
+        if (!(sel[k].flags & DMX_SEEK_NOWINDOW)) slots.push_back({k, sel[k].uoffset});
+    if (slots.empty()) return DMX_OK;
+    if (!c->seekd.ensure(slots.size() * sizeof(SeekSlot))) return DMX_ERR_NOMEM;
+    HIPCHK(hipMemcpyAsync(c->seekd.p, slots.data(), slots.size() * sizeof(SeekSlot), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_seek_gather((const uint8_t*)d_out, c->seekd.as<SeekSlot>(), slots.size(), (uint8_t*)d_windows, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return DMX_OK;
+}
+
+int dmx_inflate_range_device(dmx_ctx* c, const void* d_in, size_t n, const dmx_seek_entry* entries, size_t count,
+                             const void* d_windows, uint64_t uoffset, size_t len, void* d_out, void* stream) {
+    if (!c || (!d_in && n) || !entries) return DMX_ERR_ARG;
+    std::vector<SeekSpan> spans;
+    if (const int rc = seek_range_plan(entries, count, n, uoffset, len, &spans); rc != DMX_OK) return rc;
+    if (spans.empty()) return DMX_OK;
+    if (!d_out || spans.size() > 0x7FFFFFFFull) return DMX_ERR_ARG;
+    for (const SeekSpan& s : spans)
+        if (s.window && !d_windows) return DMX_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    // one upload: the head {ticket 0, key all ones}, then the spans; one launch; the key back
+    const size_t bytes = sizeof(SeekSpanHead) + spans.size() * sizeof(SeekSpan);
+    if (!c->seekd.ensure(bytes)) return DMX_ERR_NOMEM;
+    if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
+    begin_timing(c, st);
+    std::vector<uint8_t> up(bytes);
+    const SeekSpanHead head{0, 0, ~0ull};
+    std::memcpy(up.data(), &head, sizeof head);
+    std::memcpy(up.data() + sizeof head, spans.data(), spans.size() * sizeof(SeekSpan));
+    SeekSpanHead* const d_head = c->seekd.as<SeekSpanHead>();
+    HIPCHK(hipMemcpyAsync(d_head, up.data(), bytes, hipMemcpyHostToDevice, st));
+    const StreamWords w((const uint8_t*)d_in);
+    if (c->timing) (void)hipEventRecord(c->ev[1], st);
+    HIPCHK(launch_inflate_spans(w.words, w.misalign, n, reinterpret_cast<const SeekSpan*>(d_head + 1),
+                                (uint32_t)spans.size(), (const uint8_t*)d_windows, (uint8_t*)d_out, d_head, c->flags,
+                                st));
+    if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    unsigned long long key = ~0ull;
+    HIPCHK(hipMemcpyAsync(&key, &d_head->key, 8, hipMemcpyDeviceToHost, st));
+    mark_end(c, st);
+    HIPCHK(hipStreamSynchronize(st));
+    end_timing(c, st);
+    const int rc = key == ~0ull ? DMX_OK : (int)(int32_t)(uint32_t)key;
+    c->stats.segments = spans.size();
+    c->stats.in_bytes = n;
     c->stats.out_bytes = rc == DMX_OK ? len : 0;
     return rc;
 }

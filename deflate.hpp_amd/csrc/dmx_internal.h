@@ -9,6 +9,7 @@
 #include "batch_table.h"      // the batch tables' records and build steps (plain C++, shared with the CPU test)
 #include "deflate_pipe.h"     // the chunk pipeline's chunk arithmetic (plain C++, shared with the CPU test)
 #include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
+#include "seek_plan.h"        // SeekSpan, SeekSpanHead, SeekSlot and the seek planners (plain C++, shared with the CPU test)
 
 namespace dmx {
 
@@ -275,6 +276,18 @@ hipError_t launch_inflate_batch_dict(const InflateBatchDesc* desc, const uint32_
                                      ::dmx_batch_result* res, unsigned int* ticket, uint32_t flags,
                                      const uint8_t* dict, uint32_t dl, hipStream_t st,
                                      const uint32_t* norder_dev = nullptr);
+
+// seek index (inflate_span.hip; the plans: seek_plan.h).
+// launch_inflate_spans: one wavefront per span on a persistent grid; span k starts at its bit of
+// the stream behind window slot spans[k].slot of `windows` and writes its bytes from `skip` on to
+// out + spans[k].out_off.  *head: {ticket 0, key all ones} from the caller; key ends as the minimum
+// of k << 32 | (uint32_t)status over the failing spans.  flags: DMX_CFG_RFC_STRICT.
+hipError_t launch_inflate_spans(const uint32_t* in_words, uint64_t misalign, uint64_t n, const SeekSpan* spans,
+                                uint32_t nspans, const uint8_t* windows, uint8_t* out, SeekSpanHead* head,
+                                uint32_t flags, hipStream_t st);
+// window slot list[b].slot of `windows` = out[list[b].uoffset - 32768, list[b].uoffset)
+hipError_t launch_seek_gather(const uint8_t* out, const SeekSlot* list, uint64_t nlist, uint8_t* windows,
+                              hipStream_t st);
 
 // Batch tables from device-resident descriptor arrays (batch_table.hip; the steps: batch_table.h).
 // launch_batch_segtab: the deflate's segment table for `count` buffers and a capacity of `cap`

@@ -397,6 +397,12 @@ int inflate_fb_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, uint8_t* fixed_
     }
     c->stats.segments = nch;
     c->last_end = (p.units[p.chain.back()].end + 7) / 8;
+    if (c->seek_tap) {  // the index's checkpoints: the chain members that start at a block header
+        c->seek_tap->cands.clear();
+        for (uint64_t k = 0; k < nch; k++)
+            if (p.expects(p.chain[k]) == FB_AT_HEADER)
+                c->seek_tap->cands.push_back({p.units[p.chain[k]].start, p.coffs[k], false});
+    }
     if (dev_out) *dev_out = out;
     return DMX_OK;
 }

@@ -178,6 +178,29 @@ int run_plan(PlanRun& s, InflateResult& r) {
     return DMX_OK;
 }
 
+// dmx_inflate_index_device: the validated chain's segment starts as the index's checkpoints.  No
+// back-reference crosses a segment start, so none needs a window.
+void seek_tap_segments(SeekTap* tap, const SegChain& ch, const uint64_t* cands) {
+    tap->cands.clear();
+    for (size_t i = 0; i < ch.chain.size(); i++) tap->cands.push_back({8 * cands[ch.chain[i]], ch.offsets[i], true});
+}
+// The same for the uniform layout, whose chain the validation kernels checked on the device: the
+// records and candidates up to the BFINAL segment come back (one more host synchronisation, in
+// the index call only) and the host walks them.  A walk that does not confirm the chain leaves
+// the tap empty (entry 0 alone: correct, degenerate).
+int seek_tap_uniform(dmx_ctx* c, const InflateArgs& A, const InflateResult& r, hipStream_t st) {
+    const uint64_t nc = std::min<uint64_t>((uint64_t)r.fin_index + 1, A.ncand);
+    std::vector<SegRecord> h(nc);
+    std::vector<uint64_t> hc(nc);
+    HIPCHK(hipMemcpyAsync(h.data(), A.recs, nc * sizeof(SegRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hc.data(), A.cands, nc * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const SegChain ch = seg_chain_walk(h.data(), hc.data(), nc);
+    c->seek_tap->cands.clear();
+    if (ch.ok && ch.total == r.total) seek_tap_segments(c->seek_tap, ch, hc.data());
+    return DMX_OK;
+}
+
 // Chain repair.  A "00 00 FF FF" inside stored data (random data: once per ~4 GiB) is a
 // candidate no segment starts at, so the candidate chain skips it and every later segment
 // sits one slot too far; the whole stream used to go to the serial decoder (hours at
@@ -242,6 +265,7 @@ int chain_repair(PlanRun& s, bool fixed, uint8_t* out, size_t cap, size_t* total
     HIPCHK(hipStreamSynchronize(st));
     end_timing(c, st);
     c->last_end = h[ch.chain.back()].end_byte;
+    if (c->seek_tap) seek_tap_segments(c->seek_tap, ch, hc.data());
     c->stats.path = 4;
     c->stats.out_bytes = ch.total;
     *total_out = ch.total;
@@ -315,7 +339,9 @@ int inflate_finish(dmx_ctx* c, PlanRun& s, const InflateResult& r, const uint8_t
         c->stats.out_bytes = r.total;
         *total_out = r.total;
         if (dev_out) *dev_out = out;
-        return r.total > cap ? DMX_ERR_CAPACITY : DMX_OK;
+        if (r.total > cap) return DMX_ERR_CAPACITY;
+        if (c->seek_tap && s.lead_mode == 4) return seek_tap_uniform(c, s.A, r, st);
+        return DMX_OK;
     }
     c->ev3_marked = false;  // (the paths below wait again: their end_timing records the end)
     if (s.lead_mode == 4 && parallel_ok && ncand > 1) {

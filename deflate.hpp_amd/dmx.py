@@ -32,6 +32,8 @@ DMX_FRAME_ZLIB = 1
 DMX_FRAME_GZIP = 2
 DMX_FRAME_BGZF = 3
 FRAME = {"zlib": DMX_FRAME_ZLIB, "gzip": DMX_FRAME_GZIP, "bgzf": DMX_FRAME_BGZF}
+DMX_SEEK_WINDOW = 32768
+DMX_SEEK_NOWINDOW = 1  # dmx_seek_entry.flags: nothing before the entry is referenced
 BATCH_PATH = 6  # dmx_batch_result.path of a stream the batch decoder took
 
 CORPUS = {"zeros": 0, "repeat": 1, "random": 2, "text": 3, "mixed": 4, "bmp": 5}
@@ -52,6 +54,7 @@ EXPORTS = [
     "dmx_deflate_batch_framed", "dmx_inflate_batch_framed", "dmx_bgzf_bound", "dmx_deflate_bgzf",
     "dmx_inflate_bgzf", "dmx_deflate_bgzf_device", "dmx_bgzf_index_device", "dmx_inflate_bgzf_device",
     "dmx_inflate_bgzf_range_device", "dmx_batch_reserve", "dmx_deflate_batch_async", "dmx_inflate_batch_async",
+    "dmx_seek_windows_bound", "dmx_inflate_index_device", "dmx_inflate_range_device",
 ]
 
 
@@ -81,6 +84,13 @@ class BatchResult(ctypes.Structure):
 class BgzfEntry(ctypes.Structure):
     """dmx_bgzf_entry: a member's start in the BGZF file and in the plain bytes."""
     _fields_ = [("coffset", ctypes.c_uint64), ("uoffset", ctypes.c_uint64)]
+
+
+class SeekEntry(ctypes.Structure):
+    """dmx_seek_entry: a checkpoint of the seek index -- a block header's stream bit, the plain
+    bytes before it, the valid bytes of its window slot (0 or 32768) and DMX_SEEK_* flags."""
+    _fields_ = [("bit", ctypes.c_uint64), ("uoffset", ctypes.c_uint64), ("window", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
 
 
 _lib = None
@@ -169,6 +179,12 @@ def lib():
     L.dmx_bgzf_index_device.argtypes = [vp, vp, sz, bep, sz, ctypes.POINTER(sz), ctypes.POINTER(u64), vp]
     L.dmx_inflate_bgzf_device.argtypes = [vp, vp, sz, u32, vp, sz, ctypes.POINTER(sz), vp]
     L.dmx_inflate_bgzf_range_device.argtypes = [vp, vp, sz, bep, sz, u64, sz, u32, vp, vp]
+    sep = ctypes.POINTER(SeekEntry)
+    L.dmx_seek_windows_bound.argtypes = [sz, sz]
+    L.dmx_seek_windows_bound.restype = sz
+    L.dmx_inflate_index_device.argtypes = [vp, vp, sz, vp, sz, sz, sep, sz, vp, sz, ctypes.POINTER(sz),
+                                           ctypes.POINTER(sz), vp]
+    L.dmx_inflate_range_device.argtypes = [vp, vp, sz, sep, sz, vp, u64, sz, vp, vp]
     _lib = L
     return L
 
@@ -187,6 +203,11 @@ def _check(rc, what):
 
 def deflate_bound(n):
     return lib().dmx_deflate_bound(n)
+
+
+def seek_windows_bound(cap, spacing=262144):
+    """Bytes of window slots that hold the seek index of any stream of at most cap plain bytes."""
+    return lib().dmx_seek_windows_bound(cap, spacing)
 
 
 def corpus(kind, n, offset=0):
@@ -640,6 +661,44 @@ class Context:
                                                    uoffset, length, DMX_VERIFY if verify else 0,
                                                    ctypes.c_void_p(d_out), ctypes.c_void_p(stream) if stream else None),
                "inflate_bgzf_range_device")
+
+    # ---- seek index and ranged reads for unblocked streams ---------------------------------
+    def inflate_index_device(self, d_in, n, d_out, cap, spacing=262144, stream=None):
+        """inflate_device plus the seek index (dmx_inflate_index_device), one call with buffers
+        sized by cap -> (out_len, entries, windows): entries a (count + 1, 4) uint64 array of
+        (bit, uoffset, window, flags), the last row the sentinel; windows a uint8 CUDA tensor whose
+        slot k, bytes [k * 32768, (k + 1) * 32768), goes with row k.  A DMX_ERR_CAPACITY error
+        carries the output size that was needed as .needed."""
+        import numpy as np
+        import torch
+        wcap = seek_windows_bound(cap, spacing)
+        ecap = wcap // DMX_SEEK_WINDOW + 1
+        windows = torch.empty(max(wcap, 1), dtype=torch.uint8, device="cuda")
+        ent = (SeekEntry * max(ecap, 1))()
+        count, out_len = ctypes.c_size_t(), ctypes.c_size_t()
+        rc = lib().dmx_inflate_index_device(self.h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out), cap, spacing,
+                                            ent, ecap, ctypes.c_void_p(windows.data_ptr()), wcap,
+                                            ctypes.byref(count), ctypes.byref(out_len),
+                                            ctypes.c_void_p(stream) if stream else None)
+        self._check_needed(rc, "inflate_index_device", out_len.value)
+        rows = [(e.bit, e.uoffset, e.window, e.flags) for e in ent[:count.value + 1]]
+        return out_len.value, np.array(rows, dtype=np.uint64).reshape(-1, 4), windows[:count.value * DMX_SEEK_WINDOW]
+
+    def inflate_range_device(self, d_in, n, entries, windows, uoffset, length, d_out, stream=None):
+        """Plain bytes [uoffset, uoffset + length) into device pointer d_out, decoding only from
+        the checkpoints that cover them (dmx_inflate_range_device); entries and windows: what
+        inflate_index_device returned for the stream (windows: a tensor, a device pointer or None)."""
+        import numpy as np
+        idx = np.ascontiguousarray(entries, dtype=np.uint64)
+        if idx.ndim != 2 or idx.shape[1] != 4 or idx.shape[0] < 1:
+            raise ValueError("entries must be a (count + 1, 4) array")
+        ent = (SeekEntry * idx.shape[0])(*[SeekEntry(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF,
+                                                     int(r[3]) & 0xFFFFFFFF) for r in idx])
+        wp = windows.data_ptr() if hasattr(windows, "data_ptr") else windows
+        _check(lib().dmx_inflate_range_device(self.h, ctypes.c_void_p(d_in), n, ent, idx.shape[0] - 1,
+                                              ctypes.c_void_p(wp) if wp else None, uoffset, length,
+                                              ctypes.c_void_p(d_out), ctypes.c_void_p(stream) if stream else None),
+               "inflate_range_device")
 
     def set_timing(self, on=True):
         _check(lib().dmx_set_timing(self.h, 1 if on else 0), "set_timing")

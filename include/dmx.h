@@ -514,6 +514,78 @@ int dmx_inflate_bgzf_range_device(dmx_ctx* ctx, const void* d_in, size_t n, cons
                                   size_t members, uint64_t uoffset, size_t len, uint32_t flags, void* d_out,
                                   void* stream);
 
+/* ---- seek index and ranged reads for unblocked streams (zran's idea; not in the reference) -----
+ * BGZF is blocked for random access; an ordinary zlib / gzip / pigz stream and libdmx's own output
+ * are not.  These calls build a zran-style index while a stream is decoded once -- checkpoints at
+ * block headers, each with the 32 KiB of plain bytes before it -- and then read any range by
+ * decoding only from the checkpoint before it.  Raw RFC 1951 streams: the caller passes the
+ * stream inside a zlib or gzip file, and every `bit` is relative to that pointer.  The calls take
+ * the context mutex, are ordered against the context's other deflate / inflate work like their
+ * siblings, run on `stream` (NULL: the context's stream) and return after their last host
+ * synchronisation.  A null context is DMX_ERR_ARG.
+ *
+ * dmx_inflate_index_device: dmx_inflate_device plus the index.  Bytes, *out_len, error codes and
+ * the DMX_ERR_CAPACITY behaviour are dmx_inflate_device's; no index is promised on error (*count =
+ * 0).  spacing: the least number of plain bytes between two checkpoints; below 32768 is
+ * DMX_ERR_ARG.  *count = the checkpoints; count + 1 entries are written to HOST memory, entry 0 =
+ * {0, 0, 0, DMX_SEEK_NOWINDOW} always, the last one the sentinel {8 * the stream's end byte, plain
+ * bytes, 0, 0}.  entry_cap < count + 1 or windows_cap < count * 32768: DMX_ERR_CAPACITY with *count
+ * set; the decoded bytes in d_out are valid.  Window slot k is d_windows + k * 32768 (device
+ * memory, any alignment; 16-byte aligned is faster) and holds plain bytes [uoffset - 32768,
+ * uoffset) for the entries without DMX_SEEK_NOWINDOW; the other slots are not written.
+ * dmx_seek_windows_bound(cap, spacing) = (cap / spacing + 2) * 32768 bounds count * 32768 for any
+ * stream of at most cap plain bytes: 12.5 % of cap at a spacing of 256 KiB.
+ * Where the checkpoints come from: the block-parallel decoder (dmx_stats.path 5; zlib's, pigz's,
+ * libdeflate's streams) gives the block headers its units start at; the lane decoder (path 4,
+ * libdmx's own streams) gives the segment starts, all DMX_SEEK_NOWINDOW.  Of those, one is kept
+ * when it is at least `spacing` plain bytes past the last kept one.  Every other path (the serial
+ * decoder, the workgroup decoders) gives count = 1, entry 0 alone: correct but degenerate -- a
+ * ranged read then decodes from the stream's start.  So does a stream that is one huge block:
+ * there are no checkpoints inside a block.
+ * Host synchronisations: those of dmx_inflate_device, plus 1 when window slots are written (the
+ * gather kernel's completion) and 1 on path 4's uniform layout (the segment records).
+ *
+ * dmx_inflate_range_device: exactly plain bytes [uoffset, uoffset + len) at d_out (any alignment;
+ * nothing is written past d_out + len), given the index (HOST memory, count + 1 entries as above)
+ * and its windows.  Entry k covers [uoffset_k, uoffset_{k+1}); one wavefront per touched entry
+ * starts at its bit behind its window and stops after its byte count, all in one launch.
+ * len == 0: DMX_OK, nothing launched.  DMX_ERR_ARG: uoffset + len beyond the sentinel's uoffset,
+ * the sentinel's bit beyond 8 * n, entries not strictly increasing in uoffset (the sentinel may
+ * equal the last entry), an entry without DMX_SEEK_NOWINDOW whose window is not 32768.  Every entry
+ * is looked at on every call (count steps on the host); only the uoffset order and the windows are
+ * validated.  The entries' `bit` values are not: one that is not a block header of this stream, or
+ * lies beyond 8 * n, ends in the decoded status of the span that starts there (DMX_ERR_DATA or
+ * DMX_ERR_OVERREAD), never in a read outside [d_in, d_in + n) or a write outside [d_out, d_out +
+ * len).  Otherwise the status is the first failing entry's: DMX_ERR_OVERREAD when it runs past n, DMX_ERR_DATA on an
+ * undecodable code or when the final block ends before the byte count (the index does not belong
+ * to the stream); d_out may then hold partial output.  DMX_CFG_RFC_STRICT and the lenient cases are
+ * those of the batch decoder; a distance that reaches before the window copies nothing.
+ * Host synchronisations: 1.  dmx_last_stats after it: segments = the spans decoded, in_bytes = n,
+ * out_bytes = len (0 on error), path = 0 (no single-stream path ran).
+ *
+ * Not covered: checkpoints inside a block, containers, checksums of ranges, host-buffer forms,
+ * graph capture, streams whose plain bytes do not fit the device. */
+#define DMX_SEEK_WINDOW   32768u
+#define DMX_SEEK_NOWINDOW 1u   /* entry flag: nothing before this point is referenced (libdmx segment start, or offset 0) */
+typedef struct dmx_seek_entry {
+    uint64_t bit;      /* stream bit of a block header (BFINAL bit), relative to d_in */
+    uint64_t uoffset;  /* plain bytes before it */
+    uint32_t window;   /* valid bytes in this entry's window slot: 0 or 32768 */
+    uint32_t flags;    /* DMX_SEEK_* */
+} dmx_seek_entry;      /* 24 bytes */
+
+size_t dmx_seek_windows_bound(size_t cap, size_t spacing);   /* (cap / spacing + 2) * 32768; 0 for spacing < 32768 */
+
+int dmx_inflate_index_device(dmx_ctx* ctx, const void* d_in, size_t n, void* d_out, size_t cap,
+                             size_t spacing, dmx_seek_entry* entries, size_t entry_cap,
+                             void* d_windows, size_t windows_cap,
+                             size_t* count, size_t* out_len, void* stream);
+
+int dmx_inflate_range_device(dmx_ctx* ctx, const void* d_in, size_t n,
+                             const dmx_seek_entry* entries, size_t count,
+                             const void* d_windows, uint64_t uoffset, size_t len,
+                             void* d_out, void* stream);
+
 /* ---- instrumentation -------------------------------------------------------------------- */
 typedef struct dmx_stats {
     double ms_main_kernel;  /* HIP-event time of the dominant kernel of the last call       */
