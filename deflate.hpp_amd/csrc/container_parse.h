@@ -116,6 +116,36 @@ DMX_HD inline FrameHead parse_frame(uint32_t format, const uint8_t* in, uint64_t
     return h;
 }
 
+// The gzip header alone, for a member whose end is not given (dmx_inflate_gzip_members): the
+// checks and skips of parse_frame's gzip branch without the trailer reads.  in[0, avail) is what
+// is left of the file; *head = the bytes before the raw stream.
+//   DMX_ERR_DATA      in[0] != 1f, or avail >= 2 and in[1] != 8b, or avail >= 3 and in[2] != 8
+//   DMX_ERR_OVERREAD  the header, or the header plus an 8-byte trailer, does not fit in avail
+// No byte at or beyond in + avail is read.
+DMX_HD inline int gzip_head_len(const uint8_t* in, uint64_t avail, uint64_t* head) {
+    *head = 0;
+    if (avail == 0) return DMX_ERR_OVERREAD;
+    if (in[0] != 0x1F || (avail >= 2 && in[1] != 0x8B) || (avail >= 3 && in[2] != 8)) return DMX_ERR_DATA;
+    if (avail < 18) return DMX_ERR_OVERREAD;
+    const uint32_t flg = in[3];
+    uint64_t h = 10;
+    if (flg & 4) {  // FEXTRA (bytes 10 and 11 exist: avail >= 18)
+        h = 12 + (uint64_t)((uint32_t)in[10] | ((uint32_t)in[11] << 8));
+        if (h + 8 > avail) return DMX_ERR_OVERREAD;
+    }
+    for (int z = 0; z < 2; z++) {  // FNAME, FCOMMENT: zero-terminated
+        if (flg & (8u << z)) {
+            while (h < avail && in[h]) h++;
+            h++;
+            if (h + 8 > avail) return DMX_ERR_OVERREAD;
+        }
+    }
+    if (flg & 2) h += 2;  // FHCRC
+    if (h + 8 > avail) return DMX_ERR_OVERREAD;
+    *head = h;
+    return DMX_OK;
+}
+
 // The header dmx_deflate_zlib / dmx_deflate_gzip write for `level` (frame_head_bytes(format) bytes
 // at out); BGZF: the gzip header with FEXTRA = the BC subfield, BSIZE = member - 1.
 DMX_HD inline void frame_write_head(uint32_t format, int level, uint32_t member, uint8_t* out) {

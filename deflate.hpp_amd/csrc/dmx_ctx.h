@@ -129,6 +129,8 @@ namespace dmx {
 // A developer switch of its own, read at every dmx_create (deflate_pipe.h: pipe_knob):
 //   DMX_DEFLATE_PIPE=0|1|<chunks>|s<segments>  the deflate's chunk pipeline
 //   DMX_INFLATE_SPEC=0|1|force  the synchronous inflate's speculative first pass (inflate_plan.h)
+// and one read at every dmx_inflate_gzip_members call while dmx_set_timing is on:
+//   DMX_GZM_MAIN=scan|measure  the phase dmx_stats.ms_main_kernel brackets there (else: the batch decode)
 enum : uint32_t { DIAG_PHASES = 1, DIAG_FB = 2, DIAG_RECS = 4, DIAG_DEBUG = 8, DIAG_FBT = 16 };
 struct Diag {
     uint32_t bits = 0;

@@ -371,8 +371,7 @@ int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n
 // the batch kernel wins by throughput (4096 x 64 KiB: 32 ms against 1184 ms for the loop).  The
 // threshold therefore only bounds how long one stream may hold the batch's tail: 1 MiB of
 // compressed input is ~0.3 s on one wavefront.  A rule that weighs the batch's size is the
-// follow-up.
-constexpr size_t kBatchRouteBytes = 1u << 20;
+// follow-up.  (kBatchRouteBytes: dmx_internal.h, shared with the multi-member gzip call.)
 
 // Batch inflate: k_inflate_batch decodes the streams it keeps, longest first; the routed ones
 // follow through inflate_device_locked, one after another.
@@ -1729,6 +1728,288 @@ int dmx_inflate_bgzf_range_device(dmx_ctx* c, const void* d_in, size_t n, const 
         [&] { return launch_bgzf_range_copy(d_idx, count, u0, u1, edge, out, st); });
     c->stats.out_bytes = rc == DMX_OK ? len : 0;
     return rc;
+}
+
+// ---- multi-member gzip files (gzip_members.hip; the walk: gzip_members.h) ----------------------
+extern "C++" {
+// Developer switch, read per call and only with dmx_set_timing on: which phase
+// dmx_stats.ms_main_kernel brackets -- DMX_GZM_MAIN=scan (candidate count, its host read and the
+// candidate list), =measure (the measuring pass); anything else: the batch decode.
+static int gzm_main_phase(const dmx_ctx* c) {
+    if (!c->timing) return 2;
+    const char* e = std::getenv("DMX_GZM_MAIN");
+    return e && !std::strcmp(e, "scan") ? 0 : e && !std::strcmp(e, "measure") ? 1 : 2;
+}
+
+// The file d_in[0, n) -> out[0, cap).  Scratch: c->bgzt (tile counts and offsets, the small words),
+// c->bgzc (candidates and records), c->bgzd (the gap list, then the batch's arrays) -- the BGZF
+// device calls' buffers, which like this call end synchronised and wait for c->ev_inf.
+static int gzip_members_locked(dmx_ctx* c, const uint8_t* in, size_t n, bool verify, uint8_t* out, size_t cap,
+                               dmx_bgzf_entry* entries, size_t entry_cap, size_t* members, size_t* out_len,
+                               hipStream_t st) {
+    if (c->inf_pending) HIPCHK(hipStreamWaitEvent(st, c->ev_inf, 0));
+    begin_timing(c, st);
+    const int phase = gzm_main_phase(c);
+    // ---- candidates and their records ----
+    const uint64_t nt = gzm_tiles(in, n);
+    const size_t off_offs = up16(nt * 4), off_words = off_offs + up16(scan_words(nt) * 8);
+    if (!c->bgzt.ensure(off_words + 128)) return DMX_ERR_NOMEM;
+    uint8_t* const tb = c->bgzt.as<uint8_t>();
+    uint64_t* const tile_offs = reinterpret_cast<uint64_t*>(tb + off_offs);
+    // the small words: candidate count | gap flag | gap result (2) | measuring ticket | the batch's
+    // tickets (decode, checksum) | the batch's key
+    uint64_t* const d_ncand = reinterpret_cast<uint64_t*>(tb + off_words);
+    unsigned long long* const d_flag = reinterpret_cast<unsigned long long*>(tb + off_words + 8);
+    uint64_t* const d_gapres = reinterpret_cast<uint64_t*>(tb + off_words + 16);
+    unsigned int* const d_mticket = reinterpret_cast<unsigned int*>(tb + off_words + 32);
+    unsigned int* const d_ticket = reinterpret_cast<unsigned int*>(tb + off_words + 48);
+    unsigned long long* const d_key = reinterpret_cast<unsigned long long*>(tb + off_words + 80);
+    if (phase == 0) (void)hipEventRecord(c->ev[1], st);
+    HIPCHK(launch_gzm_count(in, n, reinterpret_cast<uint32_t*>(tb), tile_offs, d_ncand, st));
+    uint64_t ncand = 0;
+    HIPCHK(hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ncand >= 0xFFFFFFFFull) return DMX_ERR_NOMEM;  // (tickets and order entries are 32-bit)
+    std::vector<GzmCand> hc;
+    std::vector<GzmRec> hr;
+    std::vector<GzmRow> rows;
+    std::vector<GzmGap> gaps;
+    std::vector<uint64_t> uoffs;   // rows[k]'s first plain byte
+    std::vector<uint32_t> small;   // the rows the batch decodes (the others are long: decoded in the walk)
+    try {
+        hc.resize(ncand);
+        hr.resize(ncand);
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    const size_t off_recs = up16(ncand * sizeof(GzmCand));
+    if (!c->bgzc.ensure(off_recs + ncand * sizeof(GzmRec) + 16)) return DMX_ERR_NOMEM;
+    GzmCand* const d_cands = c->bgzc.as<GzmCand>();
+    GzmRec* const d_recs = reinterpret_cast<GzmRec*>(c->bgzc.as<uint8_t>() + off_recs);
+    HIPCHK(launch_gzm_write(in, n, tile_offs, d_cands, ncand, st));
+    if (phase == 0) (void)hipEventRecord(c->ev[2], st);
+    if (phase == 1) (void)hipEventRecord(c->ev[1], st);
+    int occupancy = 0;
+    HIPCHK(launch_gzm_measure(in, n, d_cands, ncand, d_recs, d_mticket, c->flags, kBatchRouteBytes, st, &occupancy));
+    if (phase == 1) (void)hipEventRecord(c->ev[2], st);
+    if (c->diag & DIAG_DEBUG)
+        std::fprintf(stderr, "dmx: gzip members: %llu candidates, measuring pass at %d workgroups per CU\n",
+                     (unsigned long long)ncand, occupancy);
+    if (ncand) {
+        HIPCHK(hipMemcpyAsync(hc.data(), d_cands, ncand * sizeof(GzmCand), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hr.data(), d_recs, ncand * sizeof(GzmRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    float phase_ms = 0;  // (read here: a long member's own call records these events anew)
+    if (phase < 2 && ncand) {
+        (void)hipEventElapsedTime(&phase_ms, c->ev[1], c->ev[2]);
+        (void)hipGetLastError();
+    }
+    // ---- the chain: the host's walk, a long member decoded where the walk meets it ----
+    uint64_t total = 0, from = 0;
+    int tail = DMX_OK;  // what ended the chain early: the first failure that is not a batch member's
+    bool bad_start = false;
+    try {
+        for (;;) {
+            const GzmWalk w = gzm_walk(hc.data(), hr.data(), ncand, n, from, &rows, &gaps);
+            for (size_t k = uoffs.size(); k < rows.size(); k++) {
+                uoffs.push_back(total);
+                small.push_back((uint32_t)k);
+                total += rows[k].plain;
+            }
+            if (w.what == GZM_DONE) break;
+            if (w.what == GZM_BAD_START) {
+                bad_start = true;
+                break;
+            }
+            if (w.what != GZM_LONG) {
+                tail = w.what;
+                break;
+            }
+            // a long member: the single-stream plan, straight into its place
+            if (!out || total > cap) {
+                tail = DMX_ERR_CAPACITY;  // (its size is not known)
+                break;
+            }
+            const GzmCand lc = hc[w.k];
+            const uint64_t s0 = lc.off + lc.head;
+            GzmCut cut = gzm_first_cut(hc.data(), ncand, w.k, n, kBatchRouteBytes);
+            size_t len = 0;
+            int rc;
+            for (;;) {
+                rc = inflate_device_locked(c, in + s0, (size_t)(cut.end - s0), out + total, cap - total, &len, nullptr, st);
+                if (rc == DMX_ERR_NOMEM || rc == DMX_ERR_DEVICE || rc == DMX_ERR_INTERNAL) return rc;
+                // DMX_ERR_OVERREAD with more of the file behind the cut: a false candidate inside the member
+                if (rc != DMX_ERR_OVERREAD || !gzm_next_cut(hc.data(), ncand, n, &cut)) break;
+            }
+            if (rc != DMX_OK) {
+                tail = rc;
+                break;
+            }
+            const uint64_t end = s0 + c->last_end;
+            if (end > n || n - end < 8) {
+                tail = DMX_ERR_OVERREAD;
+                break;
+            }
+            if (verify) {
+                uint8_t t8[8];
+                uint32_t ck = 0;
+                HIPCHK(hipMemcpyAsync(t8, in + end, 8, hipMemcpyDeviceToHost, st));
+                const int rk = checksum_locked(c, true, out + total, len, 0u, &ck, st);  // (waits for the copy too)
+                if (rk != DMX_OK) return rk;
+                if (frame_le32(t8) != ck || frame_le32(t8 + 4) != (uint32_t)len) {
+                    tail = DMX_ERR_CHECKSUM;
+                    break;
+                }
+            }
+            rows.push_back(GzmRow{lc.off, lc.head, end, len});
+            uoffs.push_back(total);
+            total += len;
+            from = end + 8;
+        }
+    } catch (const std::bad_alloc&) {
+        return DMX_ERR_NOMEM;
+    }
+    // ---- the spaces between the members: zeros, or the status of the header expected there ----
+    if (bad_start || !gaps.empty()) {
+        uint64_t longest = 0;
+        for (const GzmGap& g : gaps) longest = std::max(longest, g.b - g.a);
+        GzmGap* d_gaps = nullptr;
+        if (!bad_start) {
+            if (!c->bgzd.ensure(gaps.size() * sizeof(GzmGap))) return DMX_ERR_NOMEM;
+            d_gaps = c->bgzd.as<GzmGap>();
+            HIPCHK(hipMemcpyAsync(d_gaps, gaps.data(), gaps.size() * sizeof(GzmGap), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(launch_gzm_gaps(in, n, d_gaps, bad_start ? 0 : gaps.size(), longest, bad_start ? 0ull : ~0ull, d_flag,
+                               d_gapres, st));
+        uint64_t gr[2] = {~0ull, 0};
+        HIPCHK(hipMemcpyAsync(gr, d_gapres, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (gr[0] != ~0ull) {  // the members in front of it stay; it comes before whatever ended the walk
+            while (!rows.empty() && rows.back().coff > gr[0]) {
+                if (!small.empty() && small.back() == rows.size() - 1) small.pop_back();
+                rows.pop_back();
+                uoffs.pop_back();
+            }
+            total = rows.empty() ? 0 : uoffs.back() + rows.back().plain;
+            tail = (int)(int64_t)gr[1];
+        }
+    }
+    const size_t nrows = rows.size();
+    if (members) *members = nrows;
+    c->stats.in_bytes = n;
+    c->stats.segments = nrows;
+    c->stats.path = 6;
+    if (tail != DMX_OK) {
+        // Under DMX_VERIFY a member in front of the failure may fail its checksum, which then comes
+        // first; that needs the members' bytes, so only where they fit.
+        if (!verify || small.empty() || total > cap) return tail;
+    } else {
+        if (entries && entry_cap < nrows + 1) return DMX_ERR_CAPACITY;
+        if (total > cap) {  // before any member within the measuring limit is decoded
+            *out_len = (size_t)total;
+            return DMX_ERR_CAPACITY;
+        }
+    }
+    // ---- the members within the measuring limit: one framed batch inflate ----
+    const size_t count = small.size();
+    if (count) {
+        std::vector<uint64_t> image;
+        const size_t off_order = count * sizeof(InflateBatchDesc), off_res = off_order + up16(count * 4);
+        const size_t off_side = off_res + count * sizeof(dmx_batch_result);
+        try {
+            image.resize(off_res / 8);
+        } catch (const std::bad_alloc&) {
+            return DMX_ERR_NOMEM;
+        }
+        InflateBatchDesc* const hd = reinterpret_cast<InflateBatchDesc*>(image.data());
+        uint32_t* const ho = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(image.data()) + off_order);
+        for (size_t i = 0; i < count; i++) {  // buffer i = the member with its header and trailer
+            const GzmRow& r = rows[small[i]];
+            hd[i] = InflateBatchDesc{in + r.coff, r.end + 8 - r.coff, out + uoffs[small[i]], r.plain};
+            ho[i] = (uint32_t)i;
+        }
+        std::stable_sort(ho, ho + count, [&](uint32_t a, uint32_t b) { return hd[a].n > hd[b].n; });  // longest first
+        if (!c->bgzd.ensure(off_side + count * sizeof(FrameHead))) return DMX_ERR_NOMEM;
+        uint8_t* const base = c->bgzd.as<uint8_t>();
+        InflateBatchDesc* const desc = reinterpret_cast<InflateBatchDesc*>(base);
+        const uint32_t* const order = reinterpret_cast<const uint32_t*>(base + off_order);
+        dmx_batch_result* const res = reinterpret_cast<dmx_batch_result*>(base + off_res);
+        FrameHead* const side = reinterpret_cast<FrameHead*>(base + off_side);
+        HIPCHK(hipMemcpyAsync(base, image.data(), off_res, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(res, 0xFF, count * sizeof(dmx_batch_result), st));
+        HIPCHK(hipMemsetAsync(d_key, 0xFF, 8, st));
+        HIPCHK(launch_frame_parse(desc, side, count, DMX_FRAME_GZIP, st));
+        if (phase == 2 && c->timing) (void)hipEventRecord(c->ev[1], st);
+        HIPCHK(launch_inflate_batch(desc, order, count, res, d_ticket, c->flags, st));
+        if (phase == 2 && c->timing) (void)hipEventRecord(c->ev[2], st);
+        if (verify) HIPCHK(launch_checksum_batch(desc, res, side, count, true, d_ticket + 4, st));
+        HIPCHK(launch_frame_verdict(side, res, count, DMX_FRAME_GZIP, verify, st));
+        HIPCHK(launch_gzm_status(res, desc, count, d_key, st));
+        HIPCHK(hipEventRecord(c->ev_inf, st));
+        c->inf_pending = true;
+        unsigned long long key = 0;
+        HIPCHK(hipMemcpyAsync(&key, d_key, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));  // (the image is a local: the upload has finished too)
+        if (key != ~0ull) {
+            if (members) *members = small[(size_t)(key >> 32)];
+            end_timing(c, st);
+            return (int)(int32_t)(uint32_t)key;
+        }
+    }
+    end_timing(c, st);
+    if (phase < 2) c->stats.ms_main_kernel = phase_ms;
+    if (tail != DMX_OK) return tail;
+    if (entries) {
+        for (size_t k = 0; k < nrows; k++) entries[k] = dmx_bgzf_entry{rows[k].coff, uoffs[k]};
+        entries[nrows] = dmx_bgzf_entry{n, total};
+    }
+    c->stats.out_bytes = total;
+    *out_len = (size_t)total;
+    return DMX_OK;
+}
+}  // extern "C++"
+
+int dmx_inflate_gzip_members_device(dmx_ctx* c, const void* d_in, size_t n, uint32_t flags, void* d_out, size_t cap,
+                                    dmx_bgzf_entry* entries, size_t entry_cap, size_t* members, size_t* out_len,
+                                    void* stream) {
+    if (!c || !out_len || (!d_in && n) || (!d_out && cap) || (flags & ~DMX_VERIFY)) return DMX_ERR_ARG;
+    *out_len = 0;
+    if (members) *members = 0;
+    if (!n) {  // no member
+        if (entries && entry_cap < 1) return DMX_ERR_CAPACITY;
+        if (entries) entries[0] = dmx_bgzf_entry{0, 0};
+        return DMX_OK;
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    return gzip_members_locked(c, static_cast<const uint8_t*>(d_in), n, (flags & DMX_VERIFY) != 0,
+                               static_cast<uint8_t*>(d_out), cap, entries, entry_cap, members, out_len, st);
+}
+
+int dmx_inflate_gzip_members(dmx_ctx* c, const uint8_t* in, size_t n, uint32_t flags, uint8_t* out, size_t cap,
+                             size_t* members, size_t* out_len) {
+    if (!c || !out_len || (!in && n) || (!out && cap) || (flags & ~DMX_VERIFY)) return DMX_ERR_ARG;
+    *out_len = 0;
+    if (members) *members = 0;
+    if (!n) return DMX_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return DMX_ERR_DEVICE;
+    // the file and the output area, staged in context scratch (nothing else in this call uses it)
+    const size_t off_out = up16(n + 16);
+    if (!c->bgzs.ensure(off_out + cap + 16)) return DMX_ERR_NOMEM;
+    uint8_t* const d_in = c->bgzs.as<uint8_t>();
+    uint8_t* const d_out = cap ? d_in + off_out : nullptr;
+    HIPCHK(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, c->stream));
+    const int rc = gzip_members_locked(c, d_in, n, (flags & DMX_VERIFY) != 0, d_out, cap, nullptr, 0, members, out_len,
+                                       c->stream);
+    if (rc != DMX_OK || !*out_len) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, *out_len, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return DMX_OK;
 }
 
 // ---- seek index and ranged reads for unblocked streams ----------------------------------------

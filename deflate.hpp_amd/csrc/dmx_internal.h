@@ -10,12 +10,17 @@
 #include "deflate_pipe.h"     // the chunk pipeline's chunk arithmetic (plain C++, shared with the CPU test)
 #include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
 #include "seek_plan.h"        // SeekSpan, SeekSpanHead, SeekSlot and the seek planners (plain C++, shared with the CPU test)
+#include "gzip_members.h"     // GzmCand, GzmRec and the member walk (plain C++, shared with the CPU test)
 
 namespace dmx {
 
 // (DeflateBatchSeg, DF_BATCH_LAST and InflateBatchDesc: batch_table.h)
 constexpr uint32_t kDeflateDictMax = 16384;  // dictionary bytes the deflate side uses (the last ones)
 constexpr uint32_t kInflateDictMax = 32768;  // ... and the inflate side: the DEFLATE window
+// Compressed bytes above which one wavefront is the wrong tool for a stream: the batch inflate
+// routes such a stream to the single-stream plan (dmx_host.cpp, where the measurements behind the
+// number are), and the multi-member gzip call measures a member over at most this many bytes.
+constexpr size_t kBatchRouteBytes = 1u << 20;
 
 struct DeflateArgs {
     const uint8_t* in;
@@ -373,5 +378,35 @@ hipError_t launch_bgzf_status(const ::dmx_batch_result* res, const InflateBatchD
 hipError_t launch_bgzf_pack(const uint8_t* slots, uint64_t stride, const ::dmx_batch_result* res, uint64_t count,
                             uint32_t* sizes, uint64_t* offs, unsigned long long* key, uint8_t* out, uint64_t cap,
                             BgzfChainHead* head, hipStream_t st);
+
+
+// multi-member gzip files in device memory (gzip_members.hip; the walk: gzip_members.h).
+// tiles of the candidate scan (0 for n == 0) and a tile's bytes; tile_counts holds as many words,
+// tile_offs scan_words(tiles) entries
+uint64_t gzm_tiles(const uint8_t* in, uint64_t n);
+uint32_t gzm_tile_bytes();
+// *ncand = the offsets of in[0, n) where 1f 8b 08 starts a header that gzip_head_len accepts (n > 0)
+hipError_t launch_gzm_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts, uint64_t* tile_offs,
+                            uint64_t* ncand, hipStream_t st);
+// the candidates in offset order, for the ncand the host read back
+hipError_t launch_gzm_write(const uint8_t* in, uint64_t n, const uint64_t* tile_offs, GzmCand* cands,
+                            uint64_t ncand, hipStream_t st);
+// recs[k] = candidate k's stream measured over at most `limit` bytes, one wavefront per candidate
+// on a persistent grid (*ticket is zeroed by the launch).  flags: DMX_CFG_RFC_STRICT.  *occupancy
+// (or nullptr): the workgroups per compute unit the runtime reported for the kernel.
+hipError_t launch_gzm_measure(const uint8_t* in, uint64_t n, const GzmCand* cands, uint64_t ncand, GzmRec* recs,
+                              unsigned int* ticket, uint32_t flags, uint64_t limit, hipStream_t st,
+                              int* occupancy = nullptr);
+// res[0] = the least offset of a non-zero byte in the ngaps ranges (device memory, file order;
+// longest: the longest range's bytes), all ones when there is none; res[1] = the status of a gzip
+// header at that offset.  forced != all ones: the ranges are not looked at, res = {forced, the
+// status of a header there}.  *flag: a scratch word.
+hipError_t launch_gzm_gaps(const uint8_t* in, uint64_t n, const GzmGap* gaps, uint64_t ngaps, uint64_t longest,
+                           uint64_t forced, unsigned long long* flag, uint64_t* res, hipStream_t st);
+// *key (preset to all ones by the caller) = min over the members whose result is not DMX_OK of
+// index << 32 | (uint32_t)status; a decoded size other than desc[k].cap, the size the measuring
+// pass found, is DMX_ERR_INTERNAL
+hipError_t launch_gzm_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
+                             unsigned long long* key, hipStream_t st);
 
 }  // namespace dmx

@@ -55,6 +55,7 @@ EXPORTS = [
     "dmx_inflate_bgzf", "dmx_deflate_bgzf_device", "dmx_bgzf_index_device", "dmx_inflate_bgzf_device",
     "dmx_inflate_bgzf_range_device", "dmx_batch_reserve", "dmx_deflate_batch_async", "dmx_inflate_batch_async",
     "dmx_seek_windows_bound", "dmx_inflate_index_device", "dmx_inflate_range_device",
+    "dmx_inflate_gzip_members_device", "dmx_inflate_gzip_members",
 ]
 
 
@@ -179,6 +180,9 @@ def lib():
     L.dmx_bgzf_index_device.argtypes = [vp, vp, sz, bep, sz, ctypes.POINTER(sz), ctypes.POINTER(u64), vp]
     L.dmx_inflate_bgzf_device.argtypes = [vp, vp, sz, u32, vp, sz, ctypes.POINTER(sz), vp]
     L.dmx_inflate_bgzf_range_device.argtypes = [vp, vp, sz, bep, sz, u64, sz, u32, vp, vp]
+    L.dmx_inflate_gzip_members_device.argtypes = [vp, vp, sz, u32, vp, sz, bep, sz, ctypes.POINTER(sz),
+                                                  ctypes.POINTER(sz), vp]
+    L.dmx_inflate_gzip_members.argtypes = [vp, vp, sz, u32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     sep = ctypes.POINTER(SeekEntry)
     L.dmx_seek_windows_bound.argtypes = [sz, sz]
     L.dmx_seek_windows_bound.restype = sz
@@ -661,6 +665,51 @@ class Context:
                                                    uoffset, length, DMX_VERIFY if verify else 0,
                                                    ctypes.c_void_p(d_out), ctypes.c_void_p(stream) if stream else None),
                "inflate_bgzf_range_device")
+
+    # ---- multi-member gzip files ---------------------------------------------------------------
+    def inflate_gzip_members_device(self, d_in, n, d_out, cap, verify=True, want_index=False, stream=None):
+        """gzip.decompress of the gzip file (one or more members back to back, zero padding allowed)
+        at device pointer d_in, into device pointer d_out (dmx_inflate_gzip_members_device) ->
+        (plain bytes, members), with want_index also the (members + 1, 2) uint64 array of
+        bgzf_index_device: row k = member k's first header byte and the plain bytes before it, the
+        last row the sentinel (n, plain bytes).  A DMX_ERR_CAPACITY error carries the output size
+        that was needed as .needed (0: not known)."""
+        import numpy as np
+        sp = ctypes.c_void_p(stream) if stream else None
+        fl = DMX_VERIFY if verify else 0
+        out_len, m = ctypes.c_size_t(), ctypes.c_size_t()
+        ecap = 4096 if want_index else 0
+        while True:
+            idx = np.zeros((max(ecap, 1), 2), dtype=np.uint64)
+            ent = idx.ctypes.data_as(ctypes.POINTER(BgzfEntry)) if want_index else None
+            rc = lib().dmx_inflate_gzip_members_device(self.h, ctypes.c_void_p(d_in), n, fl, ctypes.c_void_p(d_out), cap,
+                                                       ent, ecap, ctypes.byref(m), ctypes.byref(out_len), sp)
+            if rc == DMX_ERR_CAPACITY and want_index and ecap < m.value + 1:  # the table was too small
+                ecap = m.value + 1
+                continue
+            break
+        self._check_needed(rc, "inflate_gzip_members_device", out_len.value)
+        return (out_len.value, m.value, idx[:m.value + 1].copy()) if want_index else (out_len.value, m.value)
+
+    def decompress_gzip_members(self, data, verify=True, cap=None):
+        """gzip.decompress: a gzip file of one or more members -> bytes (dmx_inflate_gzip_members).
+        cap=None starts at max(1 MiB, 8 * len(data)); on DMX_ERR_CAPACITY the call is repeated with
+        the size needed where that is reported, else with twice the capacity, bounded by DEFLATE's
+        largest expansion, 1032 * len(data) + 65536."""
+        data = bytes(data)
+        limit = 1032 * len(data) + 65536
+        given = cap is not None
+        cap = max(1 << 20, 8 * len(data)) if cap is None else cap
+        while True:
+            out = ctypes.create_string_buffer(max(cap, 1))
+            n, m = ctypes.c_size_t(), ctypes.c_size_t()
+            rc = lib().dmx_inflate_gzip_members(self.h, data, len(data), DMX_VERIFY if verify else 0, out, cap,
+                                                ctypes.byref(m), ctypes.byref(n))
+            if rc == DMX_ERR_CAPACITY and not given and cap < limit:
+                cap = n.value if n.value > cap else min(2 * cap, limit)
+                continue
+            self._check_needed(rc, "inflate_gzip_members", n.value)
+            return out.raw[: n.value]
 
     # ---- seek index and ranged reads for unblocked streams ---------------------------------
     def inflate_index_device(self, d_in, n, d_out, cap, spacing=262144, stream=None):

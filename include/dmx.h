@@ -424,8 +424,8 @@ int dmx_inflate_gzip(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, 
  * carries no checksum verdict.  A header error has bytes = 0.  Streams are routed by n[i] as in
  * the plain batch (DMX_BATCH_NO_ROUTE honoured) with the same framing and verification.
  *
- * Not covered: preset dictionaries, multi-member gzip without BSIZE, files (BGZF files: the
- * dmx_*_bgzf* calls below), graph capture. */
+ * Not covered: preset dictionaries, files (BGZF files: the dmx_*_bgzf* calls below; a gzip file of
+ * several members whose extents are not known: dmx_inflate_gzip_members below), graph capture. */
 #define DMX_FRAME_ZLIB 1u   /* RFC 1950 */
 #define DMX_FRAME_GZIP 2u   /* RFC 1952, one member per buffer */
 #define DMX_FRAME_BGZF 3u   /* gzip member whose FEXTRA holds the BC subfield (BSIZE = member size - 1) */
@@ -498,8 +498,8 @@ int dmx_inflate_bgzf(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, 
  * is not monotone: DMX_ERR_ARG.  len == 0: DMX_OK, nothing launched.  Verification (DMX_VERIFY)
  * and the ISIZE rule cover the touched members only.  Host synchronisations: 1.
  *
- * Not covered: preset dictionaries, multi-member gzip without BSIZE, graph capture; the host forms
- * above do not go through these calls yet. */
+ * Not covered: preset dictionaries, graph capture; the host forms above do not go through these
+ * calls yet.  (Multi-member gzip without BSIZE: dmx_inflate_gzip_members below.) */
 typedef struct dmx_bgzf_entry {
     uint64_t coffset; /* the member's first byte in the BGZF file   */
     uint64_t uoffset; /* its first byte in the plain (inflated) file */
@@ -513,6 +513,70 @@ int dmx_inflate_bgzf_device(dmx_ctx* ctx, const void* d_in, size_t n, uint32_t f
 int dmx_inflate_bgzf_range_device(dmx_ctx* ctx, const void* d_in, size_t n, const dmx_bgzf_entry* index,
                                   size_t members, uint64_t uoffset, size_t len, uint32_t flags, void* d_out,
                                   void* stream);
+
+/* ---- multi-member gzip files (RFC 1952 2.2; not in the reference) --------------------------------
+ * A gzip FILE is a series of members back to back: `cat a.gz b.gz`, a log that gzip appended to, a
+ * WARC archive with one member per record, a .gz padded with zeros to a block size.
+ * dmx_inflate_gzip and DMX_FRAME_GZIP take one member whose extent the caller knows; these calls take
+ * the file.  Python's gzip.decompress is the model: a member must start at offset 0; behind each
+ * member's 8-byte trailer zero bytes are skipped, then the file ends or the next header begins.
+ * Header checks are dmx_inflate_gzip's (magic, CM = 8; FEXTRA, FNAME, FCOMMENT, FHCRC skipped).
+ *
+ * Nothing in a header says where a member ends, so the device finds out: every offset where
+ * 1f 8b 08 starts a header that parses is a candidate, every candidate's stream is measured by one
+ * wavefront that decodes it without keeping the bytes (over at most 1 MiB of input, the batch
+ * calls' routing threshold), the host walks the chain over those records, and the members on it
+ * are decoded by one framed batch inflate -- each small member is decoded twice.  A member whose
+ * stream is longer than the measuring limit goes to the single-stream plan of dmx_inflate_device
+ * instead, one call each, decoded once unless the bytes 1f 8b 08 of a false candidate lie in it
+ * behind the limit (then once more per such candidate).
+ *
+ * dmx_inflate_gzip_members_device: DEVICE pointers, any alignment.  The members' plain bytes are
+ * written back to back at d_out, *out_len = their sum, *members (may be NULL) = the members.  With
+ * entries != NULL, members + 1 entries are written to HOST memory, the table dmx_bgzf_index_device
+ * writes: entry k = {member k's first header byte, the plain bytes before it}, the last one the
+ * sentinel {n, *out_len}.  (Padding may follow a member, so an entry does not give the member's end:
+ * no ranged read goes through this table.)  flags: DMX_VERIFY or 0.
+ *   n == 0: DMX_OK, no member, no bytes.
+ *   DMX_ERR_ARG: a null context or out_len, d_in == NULL with n > 0, d_out == NULL with cap > 0, an
+ *     unknown flag -- checked before any device work.
+ *   The status is the first failing member's, in file order.  Where a header is expected at offset
+ *     p (0, or the first non-zero byte behind a trailer) with r bytes left: DMX_ERR_DATA when
+ *     in[p] != 1f, or r >= 2 and in[p + 1] != 8b, or r >= 3 and in[p + 2] != 8; DMX_ERR_OVERREAD
+ *     when the header, or the header plus an 8-byte trailer, does not fit in r.  Then
+ *     DMX_ERR_OVERREAD when the member's stream or trailer runs past n, DMX_ERR_DATA on a stream
+ *     that cannot be decoded, and under DMX_VERIFY DMX_ERR_CHECKSUM on a CRC-32 mismatch or an
+ *     ISIZE that is not the member's plain size mod 2^32.  Decoding keeps the context's leniency
+ *     (DMX_CFG_RFC_STRICT honoured), as the batch decoder does.  On these errors *out_len = 0,
+ *     *members = the members in front of the failure, and d_out may hold partial output.
+ *   DMX_ERR_CAPACITY:
+ *     entry_cap < members + 1 with entries != NULL: *members set, *out_len = 0, d_out unspecified.
+ *     The output does not fit cap and every member is within the measuring limit: *out_len = the
+ *       exact size needed, nothing is written (the check precedes the decode).
+ *     A member beyond the measuring limit does not fit what is left of cap: *out_len = 0 (its size
+ *       is not known); earlier bytes of d_out are unspecified.  (Where long members fit and later
+ *       small ones do not, *out_len is the exact size and the long members' bytes are in d_out.)
+ *   Nothing is written outside [d_out, d_out + cap) and nothing is read outside [d_in, d_in + n),
+ *   but for the aligned loads that share a 16-byte line with a byte of the file.
+ * Host synchronisations: the candidate count; the candidates' records; the gap check, when bytes
+ * lie between or behind members; the batch's status; and per long member those of
+ * dmx_inflate_device plus, under DMX_VERIFY, its checksum.
+ *
+ * dmx_inflate_gzip_members: host buffers, the same statuses; the file is staged with one copy to
+ * the device, the device form runs there, the bytes are copied back.
+ *
+ * The calls take the context mutex, are ordered against the context's other deflate / inflate work
+ * like dmx_inflate_bgzf_device, run on `stream` (NULL: the context's stream; the host form always
+ * there) and return after their last host synchronisation.  A context with n_gpus > 1 runs them on
+ * its first device.
+ *
+ * Not covered: ranged reads through the table, writing multi-member files (BGZF does that), preset
+ * dictionaries, graph capture. */
+int dmx_inflate_gzip_members_device(dmx_ctx* ctx, const void* d_in, size_t n, uint32_t flags, void* d_out,
+                                    size_t cap, dmx_bgzf_entry* entries, size_t entry_cap, size_t* members,
+                                    size_t* out_len, void* stream);
+int dmx_inflate_gzip_members(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t* out, size_t cap,
+                             size_t* members, size_t* out_len);
 
 /* ---- seek index and ranged reads for unblocked streams (zran's idea; not in the reference) -----
  * BGZF is blocked for random access; an ordinary zlib / gzip / pigz stream and libdmx's own output
