@@ -1,6 +1,8 @@
 // dmx_ctx.h -- the context and the small pieces the host translation units share (dmx_host.cpp:
-// context, deflate, batch, containers, files, multi-GPU, C-ABI; host_inflate.cpp: the segmented
-// inflate plan, the async path, the serial fallback; host_fb.cpp: path 5).
+// context, single-stream calls, checksums, host zlib / gzip forms, seek calls, files, multi-GPU;
+// host_batch.cpp: the batch calls, synchronous, asynchronous and framed; host_members.cpp: BGZF
+// files and multi-member gzip; host_inflate.cpp: the segmented inflate plan, the async path, the
+// serial fallback; host_fb.cpp: path 5).
 //
 // A context owns one HIP device, one non-blocking stream and grow-only device scratch
 // (segment slots, size/offset arrays, candidate lists, look-back words).  Every entry point
@@ -177,6 +179,74 @@ struct StreamWords {
     explicit StreamWords(const uint8_t* d_in)
         : words(reinterpret_cast<const uint32_t*>(d_in - ((uintptr_t)d_in & 3))), misalign((uintptr_t)d_in & 3) {}
 };
+
+// What dmx_host.cpp, host_batch.cpp and host_members.cpp share among themselves.  Hidden: these
+// names stay out of the library's dynamic symbol table.
+#pragma GCC visibility push(hidden)
+
+// Restores the calling thread's current HIP device on scope exit: an entry point switches to
+// its context's device, and a caller driving several GPUs from one thread must not see its
+// current device move.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = prev == dev || hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// An entry point's prologue, behind its argument checks: locks the context, switches to its
+// device and resolves the caller's stream (null: the context's own).  DMX_ENTER(g, c[, stream])
+// declares the guard g and returns DMX_ERR_DEVICE where the switch failed, as HIPCHK does.
+struct CallGuard {
+    std::lock_guard<std::mutex> lock;
+    DeviceGuard dev;
+    const bool ok;
+    const hipStream_t st;
+    explicit CallGuard(dmx_ctx* c, void* stream = nullptr)
+        : lock(c->mu), dev(c->device), ok(dev.ok), st(stream ? (hipStream_t)stream : c->stream) {}
+};
+#define DMX_ENTER(g, ...)   \
+    CallGuard g(__VA_ARGS__); \
+    if (!g.ok) return DMX_ERR_DEVICE
+
+inline size_t up16(size_t b) { return (b + 15) & ~size_t(15); }
+// the batch deflate knows 16 and 32 KiB segments (64 KiB blocks pair front segments)
+inline bool has_batch_deflate(const dmx_ctx* c) { return c->seg == 16384 || c->seg == 32768; }
+
+// dmx_host.cpp
+// The deflate's scratch for nseg segments, of which the front kernel sees nfront of fseg_bytes
+// each, and the scratch half of its arguments.  false: out of device memory.
+bool deflate_scratch(dmx_ctx* c, DeflateArgs& A, uint64_t nseg, uint64_t nfront, int level, uint32_t fseg_bytes);
+// Adler-32 / CRC-32 of a device buffer, computed on the GPU (checksum.hip); the value is
+// returned to the host (the call synchronizes the stream).
+int checksum_locked(dmx_ctx* c, bool crc, const uint8_t* d, size_t n, uint32_t init, uint32_t* out, hipStream_t st);
+
+// host_batch.cpp
+// A framed batch call (dmx_*_batch_framed_device; the BGZF calls of host_members.cpp)
+struct FramePlan {
+    uint32_t format;                // DMX_FRAME_*
+    int level;                      // deflate: the level the header states
+    bool verify;                    // inflate: DMX_BATCH_VERIFY
+    const InflateBatchDesc* hdesc;  // deflate: count x {plain input, size, framed output, capacity}
+};
+int deflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count, int level,
+                         uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, hipStream_t st,
+                         const uint8_t* d_dict = nullptr, size_t dict_len = 0, const FramePlan* fp = nullptr);
+int inflate_batch_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count,
+                         uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res, uint32_t flags,
+                         hipStream_t st, const uint8_t* d_dict = nullptr, size_t dict_len = 0,
+                         const FramePlan* fp = nullptr);
+int deflate_batch_framed_locked(dmx_ctx* c, const uint8_t* const* d_in, const size_t* n, size_t count, int level,
+                                uint32_t format, uint8_t* const* d_out, const size_t* cap, dmx_batch_result* res,
+                                hipStream_t st);
+
+#pragma GCC visibility pop
 
 // host_inflate.cpp
 // candidate segment starts: counts the markers per tile and scans the counts (Scal::nmarkers

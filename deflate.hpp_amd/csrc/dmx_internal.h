@@ -18,7 +18,7 @@ namespace dmx {
 constexpr uint32_t kDeflateDictMax = 16384;  // dictionary bytes the deflate side uses (the last ones)
 constexpr uint32_t kInflateDictMax = 32768;  // ... and the inflate side: the DEFLATE window
 // Compressed bytes above which one wavefront is the wrong tool for a stream: the batch inflate
-// routes such a stream to the single-stream plan (dmx_host.cpp, where the measurements behind the
+// routes such a stream to the single-stream plan (host_batch.cpp, where the measurements behind the
 // number are), and the multi-member gzip call measures a member over at most this many bytes.
 constexpr size_t kBatchRouteBytes = 1u << 20;
 

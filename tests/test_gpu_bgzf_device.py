@@ -392,6 +392,29 @@ def test_range_verifies_the_touched_members_only(ctx):
     assert range_dev(ctx, f, lie, BLOCK, 10, verify=False)[0] == dmx.DMX_ERR_CHECKSUM
 
 
+# ---- the call's figures --------------------------------------------------------------------------------
+def stats_of(ctx):
+    s = ctx.stats()
+    return {"segments": s.segments, "path": s.path, "in_bytes": s.in_bytes, "out_bytes": s.out_bytes}
+
+
+@pytest.mark.parametrize("verify", [True, False])
+def test_stats(ctx, verify):
+    """dmx_last_stats after the two decoding calls: the members decoded (the EOF member is one),
+    path 6, and the bytes."""
+    parts = [dmx.corpus("text", 3000, offset=1), dmx.corpus("mixed", BLOCK, offset=2), dmx.corpus("text", 500, offset=3)]
+    whole = b"".join(parts)
+    f = b"".join(member(p) for p in parts) + EOF_BLOCK
+    st, got, _, _ = inflate_dev(ctx, f, verify=verify)
+    assert st == dmx.DMX_OK and got == whole
+    assert stats_of(ctx) == {"segments": 4, "path": 6, "in_bytes": len(f), "out_bytes": len(whole)}
+    # a range over the end of member 0 and the start of member 1
+    st, got, fill_ok = range_dev(ctx, f, walk(f), 2990, 100, verify=verify)
+    assert st == dmx.DMX_OK and got == whole[2990:3090] and fill_ok
+    s = stats_of(ctx)
+    assert (s["segments"], s["path"], s["out_bytes"]) == (2, 6, 100)
+
+
 # ---- stream order ------------------------------------------------------------------------------------
 def test_calls_are_ordered_on_the_callers_stream(ctx):
     n = 3 * BLOCK + 7

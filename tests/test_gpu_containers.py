@@ -63,6 +63,27 @@ def test_zlib_gzip_roundtrip_both_ways(ctx, kind, level):
     assert ctx.inflate_gzip(gzip.compress(d, 6)) == d
 
 
+ZLIB_HEAD = [b"\x78\x01", b"\x78\x01", b"\x78\x5e", b"\x78\xda"]  # per level: CMF, FLG (FLEVEL 0, 0, 1, 3)
+GZIP_XFL = [4, 4, 0, 2]
+
+
+@pytest.mark.parametrize("n", [0, 1, 70000])
+@pytest.mark.parametrize("level", [0, 1, 2, 3])
+def test_zlib_gzip_header_and_trailer_bytes(ctx, level, n):
+    """The host forms' framing, byte for byte: the header the level states, the trailer from
+    Python's checksums; and the round trip through zlib / gzip."""
+    d = dmx.corpus("text", n, offset=77)
+    z = ctx.compress_zlib(d, level)
+    assert z[:2] == ZLIB_HEAD[level]
+    assert z[-4:] == zlib.adler32(d).to_bytes(4, "big")
+    assert zlib.decompress(z) == d and ctx.inflate_zlib(z) == d
+    g = ctx.compress_gzip(d, level)
+    assert g[:10] == bytes([0x1F, 0x8B, 8, 0, 0, 0, 0, 0, GZIP_XFL[level], 0xFF])
+    assert g[-8:] == zlib.crc32(d).to_bytes(4, "little") + (n & 0xFFFFFFFF).to_bytes(4, "little")
+    assert gzip.decompress(g) == d and ctx.inflate_gzip(g) == d
+    assert z[2:-4] == g[10:-8]  # the same raw stream inside both
+
+
 def test_empty_containers(ctx):
     assert zlib.decompress(ctx.compress_zlib(b"")) == b""
     assert gzip.decompress(ctx.compress_gzip(b"")) == b""

@@ -299,6 +299,26 @@ def test_the_measuring_limit(ctx, kind):
     check_ok(ctx, f, want=want, mods=MODS[1:2] if kind == "text" else MODS[1:])
 
 
+def stats_of(ctx):
+    s = ctx.stats()
+    return {"segments": s.segments, "path": s.path, "in_bytes": s.in_bytes, "out_bytes": s.out_bytes}
+
+
+@pytest.mark.parametrize("verify", [True, False])
+def test_stats(ctx, verify):
+    """dmx_last_stats after the call: the member count (not the batch's), path 6, and the bytes --
+    for a file the batch decodes alone and for one with a long member between two short ones."""
+    parts = [text(100, 1), text(101, 2), text(99, 3)]
+    f = b"".join(gz(p) for p in parts)
+    r = run(ctx, f, verify=verify)
+    assert r.status == dmx.DMX_OK and r.bytes == b"".join(parts) and r.members == 3
+    assert stats_of(ctx) == {"segments": 3, "path": 6, "in_bytes": len(f), "out_bytes": 300}
+    lf, lwant = limit_file("T+1")
+    r = run(ctx, lf, verify=verify, want=lwant)
+    assert r.status == dmx.DMX_OK and r.bytes == lwant and r.members == 4
+    assert stats_of(ctx) == {"segments": 4, "path": 6, "in_bytes": len(lf), "out_bytes": len(lwant)}
+
+
 def test_long_member_with_a_false_candidate_behind_its_limit(ctx):
     inner = gz(text(500, 1), name=b"inner.txt")
     pay = text(1200 << 10, 30) + inner + text(800 << 10, 31)
