@@ -1458,6 +1458,16 @@ __global__ __launch_bounds__(DF_NT) __attribute__((amdgpu_num_vgpr(52))) void k_
 // segment's HBM slot in whole words.  Every step is wave-synchronous (no workgroup barrier):
 // the serial parts of a segment (the code build, the header) overlap other segments' work in
 // the other waves of the CU instead of idling fifteen waves of a 1024-thread workgroup.
+//
+// What a wave carries from pass to pass stays in registers: the segment's first block of token
+// words and its word count (read from HBM once, before the histogram; later blocks are read
+// again by the packing pass), the class sizes, start ranks and next codes of the code build
+// (one entry per lane or scalars, read with v_readlane), and per header position the run
+// length, code length and bit offset of a run start.  The ranking ballots of the code build run
+// over the distinct values a 64-symbol chunk holds, a chunk without a used symbol is passed
+// over, and the staging window is cleared only as far as the block, whose exact size is known
+// by then, can reach.  The segment index is wave-uniform by construction and is declared so
+// (v_readfirstlane), which keeps every address derived from it on the scalar side.
 // ---------------------------------------------------------------------------------------
 constexpr int EM_NW = 4;          // waves (segments) per 256-thread workgroup
 constexpr int EM_FLUSH = 256;     // staged whole words that trigger a flush to HBM
@@ -1472,16 +1482,10 @@ struct EmWave {
     };
     uint32_t code[EM_SYM];   // (len << 16) | bit-reversed code
     uint8_t len[EM_SYM];
-    uint16_t rk[EM_SYM];     // per symbol slot: half-class | rank in it, then rank in its length;
-                             // per header position: run length (run starts), then run bit offset
+    uint16_t rk[6 * 64];     // per symbol slot of a chunk with a used symbol: half-class | rank in it << 5
     uint32_t prefreq[20];
     uint32_t precode[20];
     uint8_t prelen[24];
-    uint32_t hcnt[6][20];    // per chunk of 64 symbols: members of half-class k (k < 20)
-    uint32_t lcnt[6][16];    // per chunk: members of code length l
-    uint32_t kpre[2][20];    // per alphabet: members of the half-classes below k
-    uint32_t start[2][16];   // per alphabet: first rank of code length l
-    uint32_t next[2][16];    // per alphabet: first canonical code of length l
 };
 static_assert(3 * sizeof(EmWave) <= 163840 - 140320, "three emission waves fit beside a front workgroup's LDS");
 
@@ -1499,8 +1503,13 @@ __device__ __forceinline__ bool em_valid(int c, int lane) { return c < 5 ? 64 * 
 // frequency half of the class, symbol) by ballots per 64-symbol chunk, Kraft repair / slack fill
 // on the class sizes (fit_classes), lengths by rank ranges, canonical codes (RFC 1951 3.2.2;
 // reference FlatHuffmanTree::construct common.hpp:104-145).  Per-symbol state lives in LDS
-// (W.rk), not in registers.  Stands in for generateCodeLengths (common.hpp:322-404); the costs
-// feed the size compare of deflate.hpp:739-746.
+// (W.rk), not in registers; the tables that are the same for every lane (class sizes, start
+// ranks, next codes) live in registers, one entry per lane or in scalars, and are read with
+// v_readlane.  Stands in for generateCodeLengths (common.hpp:322-404); the costs feed the size
+// compare of deflate.hpp:739-746.
+__device__ __forceinline__ uint32_t em_readlane(uint32_t v, uint32_t l) {  // l wave-uniform
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
+}
 __device__ EmCodes em_build_codes(EmWave& W) {
     const int lane = lane_id();
     const uint64_t lt = (1ull << lane) - 1ull;
@@ -1517,119 +1526,129 @@ __device__ EmCodes em_build_codes(EmWave& W) {
     const uint32_t Fd = wave_sum(f5);
     const uint64_t bd = __ballot(f5 != 0);
     const uint32_t nzd = (uint32_t)__popcll(bd), hid = bd ? 64 - (uint32_t)__clzll(bd) : 0u;
-    // half-classes, their per-chunk counts (lane k holds the count of half-class k), ranks
+    // half-classes and ranks.  Lane k (lit/len) or 32 + k (distance) collects the size of
+    // half-class k in `v`; a symbol's rank in its half-class counts the members in the chunks
+    // before it too.  Only the half-classes a chunk holds get a ballot (a wave-uniform loop over
+    // the distinct values), and a chunk without a used symbol is passed over.
+    uint32_t v = 0;
     for (int c = 0; c < 6; c++) {
+        const int a = c == 5 ? 1 : 0;
         const uint32_t f = em_valid(c, lane) ? W.freq[em_slot(c, lane)] : 0u;
-        const uint32_t F = c < 5 ? Fl : Fd;
-        const uint32_t L0 = init_len(f, F, c < 5 ? DF_LIT_MAXBITS : DF_DIST_MAXBITS);
+        uint64_t rem = __ballot(f != 0);
+        if (!rem) continue;
+        const uint32_t F = a ? Fd : Fl;
+        const uint32_t L0 = init_len(f, F, a ? DF_DIST_MAXBITS : DF_LIT_MAXBITS);
         const uint32_t k0 = L0 ? 2 * L0 + init_half(f, F, L0) : 0u;
-        uint32_t mine = 0, w0 = 0;
-#pragma unroll
-        for (int k = 2; k <= 2 * DF_LIT_MAXBITS + 1; k++) {
-            const uint64_t b = __ballot(k0 == (uint32_t)k);
-            mine = lane == k ? (uint32_t)__popcll(b) : mine;
-            w0 = k0 == (uint32_t)k ? (uint32_t)__popcll(b & lt) : w0;
+        uint32_t w0 = 0;
+        while (rem) {  // f != 0 exactly where k0 >= 2: every pass ranks one half-class
+            const uint32_t kk = em_readlane(k0, (uint32_t)__builtin_ctzll(rem));
+            const uint64_t b = __ballot(k0 == kk);
+            const uint32_t home = kk + 32 * a;
+            const uint32_t before = em_readlane(v, home);
+            w0 = k0 == kk ? before + (uint32_t)__popcll(b & lt) : w0;
+            v = (uint32_t)lane == home ? before + (uint32_t)__popcll(b) : v;
+            rem &= ~b;
         }
-        if (lane < 20) W.hcnt[c][lane] = mine;
-        W.rk[64 * c + lane] = (uint16_t)(k0 | (w0 << 5));
+        W.rk[64 * c + lane] = (uint16_t)(k0 | (w0 << 5));  // k0 <= 19, w0 < 286
     }
     wave_sync();
     // class sizes per alphabet (lanes 0..19: lit/len, 32..51: distance), start ranks of the
     // half-classes (exclusive scan over k), then fit_classes and the class starts / next codes
+    uint32_t kp;             // lane k / 32 + k: members of the half-classes below k
+    uint32_t nx = 0;         // lane l / 32 + l: next canonical code of length l
+    uint32_t stl[DF_LIT_MAXBITS + 1], std_[DF_DIST_MAXBITS + 1];  // first rank of code length l (wave-uniform)
     {
-        const int a = lane >= 32 ? 1 : 0, k = lane & 31;
-        uint32_t v = 0;
-        if (k < 20) {
-            if (a) v = W.hcnt[5][k];
-            else v = W.hcnt[0][k] + W.hcnt[1][k] + W.hcnt[2][k] + W.hcnt[3][k] + W.hcnt[4][k];
-        }
+        const int k = lane & 31;
         uint32_t inc = v;  // inclusive scan inside each half (rows of 32 lanes)
 #pragma unroll
         for (int d = 1; d < 32; d <<= 1) {
             const uint32_t u = __shfl_up(inc, d, 64);
             if (k >= d) inc += u;
         }
-        if (k < 20) W.kpre[a][k] = inc - v;
+        kp = inc - v;
+    }
+    // The class sizes of an alphabet are the same for every lane: they are read out of `v` into
+    // scalars, and fit_classes runs on the scalar unit, once per alphabet.  The starts stay
+    // scalars (no class lies above the alphabet's limit, so no rank reaches a later start);
+    // lane l / 32 + l keeps the first code of length l.
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        const int maxbits = a ? DF_DIST_MAXBITS : DF_LIT_MAXBITS;
         uint32_t cnt[17];
         cnt[0] = cnt[16] = 0;
         const uint32_t nz = a ? nzd : nzl;
 #pragma unroll
         for (int L = 1; L <= 15; L++) {
-            const uint32_t x = (2 * L + 1 < 20) ? (uint32_t)__shfl(v, (a << 5) + 2 * L, 64) +
-                                                      (uint32_t)__shfl(v, (a << 5) + 2 * L + 1, 64)
-                                                : 0u;
+            const uint32_t x = L <= maxbits ? em_readlane(v, 32 * a + 2 * L) + em_readlane(v, 32 * a + 2 * L + 1) : 0u;
             cnt[L] = nz > 1 ? x : (L == 1 ? 2u : 0u);
         }
-        if (nz > 1) fit_classes(cnt, a ? DF_DIST_MAXBITS : DF_LIT_MAXBITS);
-        if (k == 0) {
-            uint32_t st = 0, code = 0;
+        if (nz > 1) fit_classes(cnt, maxbits);
+        uint32_t st = 0, code = 0;
 #pragma unroll
-            for (int L = 1; L <= 15; L++) {
-                W.start[a][L] = st;
-                st += cnt[L];
-                code = (code + cnt[L - 1]) << 1;
-                W.next[a][L] = code;
-            }
+        for (int L = 1; L <= 15; L++) {
+            if (!a && L <= DF_LIT_MAXBITS) stl[L] = st;
+            if (a && L <= DF_DIST_MAXBITS) std_[L] = st;
+            st += cnt[L];
+            code = (code + cnt[L - 1]) << 1;
+            nx = lane == 32 * a + L ? code : nx;
         }
     }
-    wave_sync();
-    // code lengths by rank; per-chunk ranks within each length
-    for (int c = 0; c < 6; c++) {
-        const int a = c == 5 ? 1 : 0;
-        const bool sym = em_valid(c, lane);
-        const uint32_t nz = a ? nzd : nzl;
-        uint32_t L = 0;
-        if (sym) {
-            const uint32_t s = c < 5 ? 64 * c + lane : (uint32_t)lane;
-            if (nz > 1) {
-                if (W.freq[em_slot(c, lane)]) {
-                    const uint32_t r = W.rk[64 * c + lane], k0 = r & 31;
-                    uint32_t q = (r >> 5) + W.kpre[a][k0];
-                    for (int c2 = 0; c2 < c && !a; c2++) q += W.hcnt[c2][k0];
-#pragma unroll
-                    for (int l = 1; l <= 15; l++) L += q >= W.start[a][l] ? 1u : 0u;
-                }
-            } else {  // zero or one used symbol: two codes of length 1 (a complete code)
-                const uint32_t u = a ? hid : hil;
-                L = (s == (u ? u - 1 : 0u) || s == (u <= 1 ? 1u : 0u)) ? 1u : 0u;
-            }
-            W.len[em_slot(c, lane)] = (uint8_t)L;
-        }
-        uint32_t mine = 0, wl = 0;
-#pragma unroll
-        for (int k = 1; k <= DF_LIT_MAXBITS; k++) {
-            const uint64_t b = __ballot(L == (uint32_t)k);
-            wl = L == (uint32_t)k ? (uint32_t)__popcll(b & lt) : wl;
-            mine = lane == k ? (uint32_t)__popcll(b) : mine;
-        }
-        if (lane < 16) W.lcnt[c][lane] = mine;
-        W.rk[64 * c + lane] = (uint16_t)wl;
-    }
-    wave_sync();
+    // code lengths by rank, then the canonical codes in the same pass: `nx` moves on by each
+    // chunk's members of a length, so a symbol's code is the next code of its length when its
+    // chunk begins plus its rank among the chunk's members of that length.  Again one ballot per
+    // distinct length in the chunk.  A chunk without a used symbol has no code at all (unless its
+    // alphabet has fewer than two used symbols: then two symbols get the length 1).
     uint32_t dyn = 0, fix = 0, hl = 0, hd = 0;
     for (int c = 0; c < 6; c++) {
         const int a = c == 5 ? 1 : 0;
         const bool sym = em_valid(c, lane);
-        const uint32_t L = sym ? W.len[em_slot(c, lane)] : 0u;
-        if (sym) {
-            const uint32_t s = c < 5 ? 64 * c + lane : (uint32_t)lane;
-            uint32_t code = 0;
-            if (L) {
-                uint32_t cc = W.next[a][L] + W.rk[64 * c + lane];
-                for (int c2 = 0; c2 < c && !a; c2++) cc += W.lcnt[c2][L];
-                code = (L << 16) | bitrev(cc, L);
+        const uint32_t nz = a ? nzd : nzl;
+        const uint32_t f = sym ? W.freq[em_slot(c, lane)] : 0u;
+        if (nz > 1 && !__ballot(f != 0)) {
+            if (sym) {
+                W.len[em_slot(c, lane)] = 0;
+                W.code[em_slot(c, lane)] = 0;
             }
-            W.code[em_slot(c, lane)] = code;
-            const uint32_t f = W.freq[em_slot(c, lane)];
+            continue;
+        }
+        const uint32_t s = c < 5 ? 64 * c + lane : (uint32_t)lane;
+        uint32_t L = 0;
+        if (nz > 1) {
+            const uint32_t r = W.rk[64 * c + lane];
+            const uint32_t q = (r >> 5) + (uint32_t)__shfl(kp, (int)((r & 31) + 32 * a), 64);
+            uint32_t l = 0;
+#pragma unroll
+            for (int i = 1; i <= DF_LIT_MAXBITS; i++) {
+                const uint32_t st = a ? (i <= DF_DIST_MAXBITS ? std_[i] : 0xFFFFFFFFu) : stl[i];
+                l += q >= st ? 1u : 0u;
+            }
+            L = f ? l : 0u;
+        } else if (sym) {  // zero or one used symbol: two codes of length 1 (a complete code)
+            const uint32_t u = a ? hid : hil;
+            L = (s == (u ? u - 1 : 0u) || s == (u <= 1 ? 1u : 0u)) ? 1u : 0u;
+        }
+        if (sym) W.len[em_slot(c, lane)] = (uint8_t)L;
+        uint64_t rem = __ballot(L != 0);
+        if (rem) {
+            const uint32_t h = 64 - (uint32_t)__clzll(rem);
+            if (a) hd = h;
+            else hl = 64 * c + h;
+        }
+        uint32_t cc = 0;
+        while (rem) {
+            const uint32_t kk = em_readlane(L, (uint32_t)__builtin_ctzll(rem));
+            const uint64_t b = __ballot(L == kk);
+            const uint32_t home = kk + 32 * a;
+            const uint32_t first = em_readlane(nx, home);
+            cc = L == kk ? first + (uint32_t)__popcll(b & lt) : cc;
+            nx = (uint32_t)lane == home ? first + (uint32_t)__popcll(b) : nx;
+            rem &= ~b;
+        }
+        if (sym) {
+            W.code[em_slot(c, lane)] = L ? (L << 16) | bitrev(cc, L) : 0u;
             const uint32_t ex = a ? dist_extra(s) : (s > 256 ? len_extra(s) : 0u);
             dyn += f * (L + ex);
             fix += f * ((a ? 5u : fixed_lit_len(s)) + ex);
-        }
-        const uint64_t used = __ballot(L != 0);
-        if (used) {
-            const uint32_t h = 64 - (uint32_t)__clzll(used);
-            if (a) hd = h;
-            else hl = 64 * c + h;
         }
     }
     wave_sync();
@@ -1769,8 +1788,13 @@ __device__ __forceinline__ uint32_t em_stored_hdr(uint32_t q, bool fin, uint32_t
 // one histogram, one code, one header -- so the block is a 64 KiB DEFLATE block whose second
 // half simply never refers into the first (valid: a reference may, but need not, reach back).
 template <int SEG, bool RAW, bool BATCH>
-__device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
+__device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg_of_wave) {
     static_assert(!BATCH || SEG <= 32768, "a batch does not pair front segments into 64 KiB blocks");
+    // the segment is the wave's, not the lane's: said so, everything addressed by it (its
+    // descriptor, word count, slot) is loaded and kept on the scalar side in the four-wave
+    // kernels too, where it comes from threadIdx.x >> 6
+    const uint64_t seg = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)seg_of_wave) |
+                         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(seg_of_wave >> 32)) << 32);
     constexpr uint32_t NH = SEG > 32768 ? 2u : 1u;  // front segments per block
     constexpr uint32_t HB = (uint32_t)SEG / NH;
     const int lane = lane_id();
@@ -1790,14 +1814,25 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
 
     if (A.level != 0) {
         // ---- histogram ------------------------------------------------------------------
+        // The first part's source and its first block of words stay in registers from here to
+        // the packing pass: a segment of at most 256 words (every terminal-run segment) reads its
+        // words, and its word count before them, from HBM once.
+        const EmSrc S0 = part(0);
+        uint32_t v0[4] = {0, 0, 0, 0};
+        if (S0.ntok) S0.load4(0, v0);
         for (int i = lane; i < EM_SYM; i += 64) W.freq[i] = 0;
         wave_sync();
         for (uint32_t h = 0; h < np; h++) {
-            const EmSrc S = part(h);
+            const EmSrc S = h == 0 ? S0 : part(h);
             const uint32_t nblk = (S.ntok + 255) / 256;
             for (uint32_t blk = 0; blk < nblk; blk++) {
                 uint32_t v[4];
-                S.load4(blk, v);
+                if (h == 0 && blk == 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) v[j] = v0[j];
+                } else {
+                    S.load4(blk, v);
+                }
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const uint32_t idx = blk * 256 + 4 * lane + j;
@@ -1833,8 +1868,12 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
             rm[c] = __ballot(start);
         }
         wave_sync();
+        // per chunk, in registers from here to the header bits: a run start's length (bits 0-8),
+        // its code length (9-12) and, once the precode is known, its bit offset (13-24); 0 elsewhere
+        uint32_t run[5];
+#pragma unroll
         for (int c = 0; c < 5; c++) {
-            uint32_t rl = 0;
+            uint32_t rl = 0, rv = 0;
             if ((rm[c] >> lane) & 1) {
                 const uint32_t i = 64 * c + lane;
                 uint32_t j = nall;
@@ -1845,13 +1884,14 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
                         if (rm[c2]) j = 64 * c2 + (uint32_t)__builtin_ctzll(rm[c2]);
                 rl = min(j, nall) - i;
                 const uint32_t v = seqv(i);
+                rv = v;
                 const RunPlan p = plan_run(v, rl);
                 if (p.n18) atomicAdd(&W.prefreq[18], p.n18);
                 if (p.n17) atomicAdd(&W.prefreq[17], p.n17);
                 if (p.n16) atomicAdd(&W.prefreq[16], p.n16);
                 if (p.nlit) atomicAdd(&W.prefreq[v], p.nlit);
             }
-            W.rk[64 * c + lane] = (uint16_t)rl;
+            run[c] = rl | (rv << 9);
         }
         wave_sync();
         wave_build_lengths64(W.prefreq, 19, DF_PRE_MAXBITS, W.prelen);
@@ -1861,18 +1901,19 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
         const uint32_t pv = lane < 19 ? W.prelen[kPerm[lane]] : 0u;
         const uint64_t nzp = __ballot(pv != 0u);
         const uint32_t hclen = max(4u, nzp ? 64u - (uint32_t)__clzll(nzp) : 0u);
-        uint32_t rtot = 0;  // run bit offsets (exclusive scan in position order) -> W.rk
+        uint32_t rtot = 0;  // run bit offsets (exclusive scan in position order; < 316 * 7 bits)
+        const uint32_t pl16 = W.prelen[16] + 2, pl17 = W.prelen[17] + 3, pl18 = W.prelen[18] + 7;
+#pragma unroll
         for (int c = 0; c < 5; c++) {
-            const uint32_t rl = W.rk[64 * c + lane];
+            const uint32_t rl = run[c] & 511u;
             uint32_t b = 0;
             if (rl) {
-                const uint32_t v = seqv(64 * c + lane);
+                const uint32_t v = run[c] >> 9;
                 const RunPlan p = plan_run(v, rl);
-                b = p.n18 * (W.prelen[18] + 7) + p.n17 * (W.prelen[17] + 3) + p.n16 * (W.prelen[16] + 2) +
-                    p.nlit * W.prelen[v];
+                b = p.n18 * pl18 + p.n17 * pl17 + p.n16 * pl16 + p.nlit * W.prelen[v];
             }
             const uint32_t inc = wave_incl_scan(b);
-            W.rk[64 * c + lane] = (uint16_t)(rl ? rtot + inc - b : 0xFFFFu);
+            if (rl) run[c] |= (rtot + inc - b) << 13;
             rtot += __shfl(inc, 63, 64);
         }
         wave_sync();
@@ -1891,8 +1932,12 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
                     W.code[s] = s < EM_LIT ? (s < 286 ? (fixed_lit_len(s) << 16) | fixed_lit_code(s) : 0u)
                                            : (s - EM_LIT < 30 ? (5u << 16) | bitrev(s - EM_LIT, 5) : 0u);
             }
+            // Clear the staging words the block can reach, not the whole window: a bit's word in
+            // the window is never above its word in the block (flushes only move bits down), and
+            // the block with its closing bytes is hbytes long.  One word of slack.
+            const uint32_t nclr = min((uint32_t)EM_STG, (uint32_t)((hbytes + 3) / 4) + 1u);
 #pragma unroll 3
-            for (int i = lane; i < EM_STG; i += 64) W.stg[i] = 0;
+            for (uint32_t i = lane; i < nclr; i += 64) W.stg[i] = 0;
             wave_sync();
             // ---- header bits ------------------------------------------------------------
             if (lane == 0) {
@@ -1903,19 +1948,13 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
             if (use_dyn) {
                 if (lane < (int)hclen) em_put(W.stg, 17 + 3 * lane, pv, 3);
                 const uint32_t rb = 17 + 3 * hclen;
+#pragma unroll
                 for (int c = 0; c < 5; c++) {
-                    const uint32_t ro = W.rk[64 * c + lane];
-                    if (ro == 0xFFFFu) continue;
-                    const uint32_t i = 64 * c + lane;
-                    const uint32_t v = seqv(i);
-                    uint32_t j = nall;  // the run's end: the next start
-                    const uint64_t m = lane < 63 ? rm[c] & (~0ull << (lane + 1)) : 0ull;
-                    if (m) j = 64 * c + (uint32_t)__builtin_ctzll(m);
-                    else
-                        for (int c2 = 4; c2 > c; c2--)
-                            if (rm[c2]) j = 64 * c2 + (uint32_t)__builtin_ctzll(rm[c2]);
-                    const RunPlan p = plan_run(v, min(j, nall) - i);
-                    uint32_t pos = rb + ro;
+                    const uint32_t rl = run[c] & 511u;
+                    if (!rl) continue;
+                    const uint32_t v = (run[c] >> 9) & 15u;
+                    const RunPlan p = plan_run(v, rl);
+                    uint32_t pos = rb + (run[c] >> 13);
                     auto put = [&](uint32_t sym, uint32_t extra, uint32_t xb) {
                         const uint32_t pc = W.precode[sym];
                         const uint32_t l = pc >> 16;
@@ -1938,12 +1977,17 @@ __device__ void em_segment(const DeflateArgs& A, EmWave& W, uint64_t seg) {
             uint32_t cur = 3 + (use_dyn ? hdr_bits : 0u);  // bit position in the window
             uint32_t* dst = slot;                          // next HBM word of the slot
             for (uint32_t h = 0; h < np; h++) {
-                const EmSrc S = part(h);
+                const EmSrc S = h == 0 ? S0 : part(h);
                 const uint32_t nblk = (S.ntok + 255) / 256;
                 for (uint32_t blk = 0; blk < nblk; blk++) {
                     uint32_t v[4], nbit[4];
                     uint64_t pat[4];
-                    S.load4(blk, v);
+                    if (h == 0 && blk == 0) {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) v[j] = v0[j];
+                    } else {
+                        S.load4(blk, v);
+                    }
                     uint32_t mine = 0;
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
