@@ -11,6 +11,7 @@
 #include "inflate_records.h"  // SegRecord, FbUnit, SEGF_*, FB_* (plain C++, shared with inflate_plan)
 #include "seek_plan.h"        // SeekSpan, SeekSpanHead, SeekSlot and the seek planners (plain C++, shared with the CPU test)
 #include "gzip_members.h"     // GzmCand, GzmRec and the member walk (plain C++, shared with the CPU test)
+#include "zip_dir.h"          // ZipHead and the ZIP directory's steps (plain C++, shared with the CPU test)
 
 namespace dmx {
 
@@ -408,5 +409,36 @@ hipError_t launch_gzm_gaps(const uint8_t* in, uint64_t n, const GzmGap* gaps, ui
 // pass found, is DMX_ERR_INTERNAL
 hipError_t launch_gzm_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
                              unsigned long long* key, hipStream_t st);
+
+// ZIP archives in device memory (zip_dir.hip; the steps: zip_dir.h).
+// *head = the end record of in[0, n), n >= 22: directory region, count, base; status DMX_ERR_DATA
+// where there is none or it spans disks
+hipError_t launch_zip_tail(const uint8_t* in, uint64_t n, ZipHead* head, hipStream_t st);
+// tiles of the candidate scan over a region (0 for len == 0); tile_counts holds as many words,
+// tile_offs scan_words(tiles) entries
+uint64_t zip_tiles(const uint8_t* reg, uint64_t len);
+// *ncand = the offsets of h's directory region where a central record starts (h.dir_size > 0)
+hipError_t launch_zip_count(const uint8_t* in, const ZipHead& h, uint32_t* tile_counts, uint64_t* tile_offs,
+                            uint64_t* ncand, hipStream_t st);
+// The entry table for the ncand the host read back, 0 < ncand and h.count <= ncand: *head = h with
+// the chain's status and the plain bytes, ents[r] (r < h.count) in directory order when the status
+// is DMX_OK.  cands: ncand entries, J: bgzf_levels(ncand) * ncand words, ents / lo / hi: h.count
+// entries, off_lo / off_hi: scan_words(h.count) entries each, totals: 2 words.
+hipError_t launch_zip_chain(const uint8_t* in, uint64_t n, const ZipHead& h, const uint64_t* tile_offs, uint64_t ncand,
+                            BgzfCand* cands, uint32_t* J, ::dmx_zip_entry* ents, uint32_t* lo, uint32_t* hi,
+                            uint64_t* off_lo, uint64_t* off_hi, uint64_t* totals, ZipHead* head, hipStream_t st);
+// Extraction of ents[0, count) (device memory; uoffset = the entry's slot in out), count > 0:
+// kind[k] = zip_job's verdict, desc[k] = {in + data_off, csize, out + slot, usize}, res[k] = the
+// result of an entry that is not extracted (a job of the host's: DMX_BATCH_DEFERRED), side[k]
+// zeroed, order = the ZIP_JOB_BATCH entries, longest class first.  work: 2 * kBatchClasses words.
+hipError_t launch_zip_jobs(const ::dmx_zip_entry* ents, uint64_t count, const uint8_t* in, uint64_t n, uint8_t* out,
+                           uint64_t route_bytes, InflateBatchDesc* desc, ::dmx_batch_result* res, FrameHead* side,
+                           uint32_t* kind, uint32_t* order, uint32_t* work, hipStream_t st);
+// the ZIP_JOB_COPY entries' bytes and results {csize, DMX_OK, 0}, one workgroup per entry
+hipError_t launch_zip_copy(const InflateBatchDesc* desc, const uint32_t* kind, uint64_t count,
+                           ::dmx_batch_result* res, hipStream_t st);
+// res[k].status of the decoded and the copied entries by zip_verdict (side[k].ck: the output's CRC-32)
+hipError_t launch_zip_verdict(const ::dmx_zip_entry* ents, const uint32_t* kind, const FrameHead* side, uint64_t count,
+                              bool verify, ::dmx_batch_result* res, hipStream_t st);
 
 }  // namespace dmx

@@ -56,6 +56,7 @@ EXPORTS = [
     "dmx_inflate_bgzf_range_device", "dmx_batch_reserve", "dmx_deflate_batch_async", "dmx_inflate_batch_async",
     "dmx_seek_windows_bound", "dmx_inflate_index_device", "dmx_inflate_range_device",
     "dmx_inflate_gzip_members_device", "dmx_inflate_gzip_members",
+    "dmx_zip_index_device", "dmx_zip_extract_device", "dmx_inflate_zip_device", "dmx_zip_index", "dmx_inflate_zip",
 ]
 
 
@@ -85,6 +86,15 @@ class BatchResult(ctypes.Structure):
 class BgzfEntry(ctypes.Structure):
     """dmx_bgzf_entry: a member's start in the BGZF file and in the plain bytes."""
     _fields_ = [("coffset", ctypes.c_uint64), ("uoffset", ctypes.c_uint64)]
+
+
+class ZipEntry(ctypes.Structure):
+    """dmx_zip_entry: one entry of a ZIP archive's central directory, 64 bytes."""
+    _fields_ = [("name_off", ctypes.c_uint64), ("data_off", ctypes.c_uint64), ("csize", ctypes.c_uint64),
+                ("usize", ctypes.c_uint64), ("uoffset", ctypes.c_uint64), ("crc", ctypes.c_uint32),
+                ("dostime", ctypes.c_uint32), ("name_len", ctypes.c_uint16), ("method", ctypes.c_uint16),
+                ("gpflags", ctypes.c_uint16), ("reserved", ctypes.c_uint16), ("status", ctypes.c_int32),
+                ("path", ctypes.c_uint32)]
 
 
 class SeekEntry(ctypes.Structure):
@@ -183,6 +193,13 @@ def lib():
     L.dmx_inflate_gzip_members_device.argtypes = [vp, vp, sz, u32, vp, sz, bep, sz, ctypes.POINTER(sz),
                                                   ctypes.POINTER(sz), vp]
     L.dmx_inflate_gzip_members.argtypes = [vp, vp, sz, u32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    zep = ctypes.POINTER(ZipEntry)
+    L.dmx_zip_index_device.argtypes = [vp, vp, sz, zep, sz, ctypes.POINTER(sz), ctypes.POINTER(u64), vp]
+    L.dmx_zip_extract_device.argtypes = [vp, vp, sz, zep, sz, ctypes.POINTER(sz), sz, u32, vp, sz, brp,
+                                         ctypes.POINTER(sz), vp]
+    L.dmx_inflate_zip_device.argtypes = [vp, vp, sz, u32, vp, sz, zep, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+    L.dmx_zip_index.argtypes = [vp, vp, sz, zep, sz, ctypes.POINTER(sz), ctypes.POINTER(u64)]
+    L.dmx_inflate_zip.argtypes = [vp, vp, sz, u32, vp, sz, zep, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     sep = ctypes.POINTER(SeekEntry)
     L.dmx_seek_windows_bound.argtypes = [sz, sz]
     L.dmx_seek_windows_bound.restype = sz
@@ -710,6 +727,94 @@ class Context:
                 continue
             self._check_needed(rc, "inflate_gzip_members", n.value)
             return out.raw[: n.value]
+
+    # ---- ZIP archives ----------------------------------------------------------------------------
+    def zip_index_device(self, d_in, n, stream=None):
+        """The central directory of the ZIP archive at device pointer d_in, read on the GPU without
+        decoding anything (dmx_zip_index_device) -> (entries, plain_bytes): a ctypes array of
+        ZipEntry in directory order and the sum of their plain sizes."""
+        sp = ctypes.c_void_p(stream) if stream else None
+        count, plain = ctypes.c_size_t(), ctypes.c_uint64()
+        ecap = 4096
+        while True:
+            ent = (ZipEntry * ecap)()
+            rc = lib().dmx_zip_index_device(self.h, ctypes.c_void_p(d_in), n, ent, ecap, ctypes.byref(count),
+                                            ctypes.byref(plain), sp)
+            if rc == DMX_ERR_CAPACITY and ecap < count.value:  # the table was too small
+                ecap = count.value
+                continue
+            break
+        _check(rc, "zip_index_device")
+        return (ZipEntry * count.value).from_buffer(ent), plain.value
+
+    def zip_extract_device(self, d_in, n, entries, d_out, cap, sel=None, verify=True, stream=None):
+        """The entries sel (indices into entries; None: all, in order) of the archive at device
+        pointer d_in, back to back at device pointer d_out (dmx_zip_extract_device) -> (out_len,
+        results): the layout's size and one BatchResult per selected entry.  A DMX_ERR_CAPACITY
+        error carries the output size that was needed as .needed."""
+        count = len(entries)
+        nsel = count if sel is None else len(sel)
+        sel_arr = None if sel is None else (ctypes.c_size_t * max(nsel, 1))(*sel)
+        res = (BatchResult * max(nsel, 1))()
+        out_len = ctypes.c_size_t()
+        rc = lib().dmx_zip_extract_device(self.h, ctypes.c_void_p(d_in), n, entries, count, sel_arr, nsel,
+                                          DMX_VERIFY if verify else 0, ctypes.c_void_p(d_out), cap, res,
+                                          ctypes.byref(out_len), ctypes.c_void_p(stream) if stream else None)
+        self._check_needed(rc, "zip_extract_device", out_len.value)
+        return out_len.value, res[:nsel]
+
+    def inflate_zip_device(self, d_in, n, d_out, cap, verify=True, stream=None):
+        """Index plus extract-all of the archive at device pointer d_in into device pointer d_out
+        (dmx_inflate_zip_device) -> (out_len, entries): entry k's bytes are d_out[uoffset, uoffset
+        + usize) where its status is DMX_OK.  A DMX_ERR_CAPACITY error for the output carries the
+        size that was needed as .needed."""
+        sp = ctypes.c_void_p(stream) if stream else None
+        fl = DMX_VERIFY if verify else 0
+        count, out_len = ctypes.c_size_t(), ctypes.c_size_t()
+        ecap = 4096
+        while True:
+            ent = (ZipEntry * ecap)()
+            rc = lib().dmx_inflate_zip_device(self.h, ctypes.c_void_p(d_in), n, fl, ctypes.c_void_p(d_out), cap, ent,
+                                              ecap, ctypes.byref(count), ctypes.byref(out_len), sp)
+            if rc == DMX_ERR_CAPACITY and ecap < count.value:  # the table was too small
+                ecap = count.value
+                continue
+            break
+        self._check_needed(rc, "inflate_zip_device", out_len.value)
+        return out_len.value, (ZipEntry * count.value).from_buffer(ent)
+
+    def unzip(self, data, names=None, verify=True):
+        """zipfile.ZipFile(...).read for every entry (names: only those) of the archive `data` ->
+        dict name -> bytes.  Names are decoded as UTF-8 when flag bit 11 is set, else cp437, as
+        zipfile does; of entries with the same name the last one is taken.  A per-entry failure
+        raises DmxError with the entry's name."""
+        import torch
+        data = bytes(data)
+        arc = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(
+            0, dtype=torch.uint8, device="cuda")
+        entries, plain = self.zip_index_device(arc.data_ptr(), len(data))
+        decoded = [data[e.name_off:e.name_off + e.name_len].decode("utf-8" if e.gpflags & 0x800 else "cp437")
+                   for e in entries]
+        last = {name: k for k, name in enumerate(decoded)}
+        if names is None:
+            sel = sorted(last.values())
+        else:
+            missing = [x for x in names if x not in last]
+            if missing:
+                raise KeyError(f"no entry named {missing[0]!r} in the archive")
+            sel = [last[x] for x in names]
+        need = sum(entries[k].usize for k in sel)
+        out = torch.empty(max(need, 1), dtype=torch.uint8, device="cuda")
+        _, res = self.zip_extract_device(arc.data_ptr(), len(data), entries, out.data_ptr(), need, sel=sel,
+                                         verify=verify)
+        host = out.cpu().numpy().tobytes()
+        got, at = {}, 0
+        for k, r in zip(sel, res):
+            if r.status != DMX_OK:
+                raise DmxError(r.status, f"unzip: entry {decoded[k]!r}")
+            got[decoded[k]] = host[at:at + entries[k].usize]
+            at += entries[k].usize
+        return got
 
     # ---- seek index and ranged reads for unblocked streams ---------------------------------
     def inflate_index_device(self, d_in, n, d_out, cap, spacing=262144, stream=None):

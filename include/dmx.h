@@ -578,6 +578,112 @@ int dmx_inflate_gzip_members_device(dmx_ctx* ctx, const void* d_in, size_t n, ui
 int dmx_inflate_gzip_members(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t* out, size_t cap,
                              size_t* members, size_t* out_len);
 
+/* ---- ZIP archives (PKWARE APPNOTE, ZIP64 included; not in the reference) ---------------------------
+ * A ZIP archive is many independent raw RFC 1951 streams (method 8) and stored byte runs (method 0)
+ * plus a central directory that states every entry's extent, plain size and CRC-32: .npz files,
+ * torch.save checkpoints, wheels, jars, docx / xlsx, zipped dataset shards.  Nothing has to be
+ * discovered and nothing is decoded twice.  Python's zipfile is the model for what parses.
+ *
+ * The directory is read on the device.  One workgroup searches the last 65557 bytes for the end
+ * record: the highest p where 50 4b 05 06 stands and p + 22 + comment length <= n.  Where the ZIP64
+ * locator (50 4b 06 07) stands at p - 20 and the ZIP64 end record (50 4b 06 06) directly in front of
+ * it, that record gives the entry count, the directory's size and its offset.  Bytes in front of the
+ * archive (a self-extractor's stub) shift every stated offset by base = end record position -
+ * directory size - directory offset, less 76 with the ZIP64 records, as zipfile does.  The central
+ * directory is a chain of variable-length records (46 bytes plus name, extra and comment); it is
+ * walked like the BGZF member chain: every offset of the directory region where 50 4b 01 02 starts a
+ * record that fits the region is a candidate, a candidate links to the one that starts where it
+ * ends, pointer doubling from the candidate at the region's first byte ranks the records.  A false
+ * signature inside a name, an extra field or a comment is never counted.  The walk must end exactly
+ * at the region's end after as many records as the end record states (zipfile ignores the count;
+ * these calls do not: 0xFFFF without a ZIP64 record is a count of 65535).  One thread per record
+ * then decodes its fields -- a ZIP64 extra 0x0001 supplies usize, csize and the local header's
+ * offset, in that order, for exactly the fields that read 0xFFFFFFFF -- and reads the local header
+ * for the data offset.  Sizes and CRC always come from the central directory, never from the local
+ * header, so a data descriptor (flag bit 3) needs nothing.  The local header's name is not compared
+ * with the central one.
+ *
+ * Per-entry status (dmx_zip_entry.status; never the return value):
+ *   DMX_ERR_ARG       flag bit 0 (encrypted), or a method other than 0 and 8
+ *   DMX_ERR_DATA      no 50 4b 03 04 at base + local header offset; a stored entry with
+ *                     csize != usize; a corrupt extra field
+ *   DMX_ERR_OVERREAD  the local header, or data_off + csize, passes n
+ *
+ * dmx_zip_index_device: the directory only, nothing is decoded.  DEVICE pointer d_in, any alignment.
+ * *count and *plain_bytes (either may be NULL) are set; with entries != NULL, *count entries are
+ * written to HOST memory in directory order.
+ *   DMX_ERR_ARG: a null context, d_in == NULL with n > 0 -- checked before any device work.
+ *   DMX_ERR_DATA: n < 22 (n == 0 included), no end record, a disk number other than 0 or more than
+ *     one disk, a negative base, a chain that does not start at the directory's first byte or does
+ *     not end at its end, a count that differs from the end record's, more than 2^63 plain bytes.
+ *   DMX_ERR_NOMEM: a directory of 2^32 - 2 candidates or more (links are 32-bit), or no memory.
+ *   DMX_ERR_CAPACITY: entry_cap < *count with entries != NULL; *count and *plain_bytes are set.
+ * Host synchronisations: 3 (the end record; the candidate count; status, plain bytes and the
+ * entries) -- 1 for an archive without entries.
+ *
+ * dmx_zip_extract_device: the entries sel[0 .. nsel) of `entries` (HOST arrays; sel == NULL: all
+ * `count` entries in order, nsel is ignored) into d_out.  Duplicates are allowed, each with its own
+ * slot; an index >= count is DMX_ERR_ARG.  The layout is the exclusive prefix sum of usize in
+ * selection order; a failing entry still owns its slot, whose bytes are unspecified.  res: a HOST
+ * array of one dmx_batch_result per selected entry (bytes = usize on DMX_OK; path = 6 for the batch
+ * decoder, the single-stream plan's path for a deflated entry above the batch calls' routing
+ * threshold of 1 MiB compressed, 0 for a stored entry).  A bad entry never disturbs its neighbours.
+ * *out_len = the layout's size.  flags: DMX_VERIFY or 0.
+ *   The sum of usize above cap: DMX_ERR_CAPACITY, *out_len = the size needed, nothing is written
+ *     (the check precedes every decode); a sum beyond 2^63: DMX_ERR_DATA.
+ *   The entries are the caller's and so untrusted again: an entry whose status is not DMX_OK keeps
+ *     it, flags and method are classified again, data_off + csize > n is that entry's
+ *     DMX_ERR_OVERREAD.  No entry causes a read outside [d_in, d_in + n) -- but for the aligned loads
+ *     that share a 16-byte line with a byte of the archive -- or a write outside its slot.
+ *   A decoded size other than usize, or a stream that does not fit its slot, is that entry's
+ *     DMX_ERR_CHECKSUM with or without DMX_VERIFY: the layout rests on usize (the BGZF ISIZE rule).
+ *     Under DMX_VERIFY a CRC-32 of the output that differs from the directory's is
+ *     DMX_ERR_CHECKSUM too.  Stream errors are the batch decoder's (DMX_ERR_DATA, DMX_ERR_OVERREAD).
+ * Host synchronisations: 1, the read-back of res (nsel == 0: none); every entry above the routing
+ * threshold adds those of dmx_inflate_device (deflated) or none (stored: one device-to-device copy)
+ * plus, under DMX_VERIFY, its checksum's.
+ *
+ * dmx_inflate_zip_device: index plus extract-all in one call; the descriptors are built from the
+ * table the index left on the device.  entries (HOST memory, entry_cap of them; required) receive
+ * *count entries with status and path as the extraction left them.  The return value covers the
+ * archive (the index's errors; DMX_ERR_CAPACITY for entry_cap < *count, *count set, or for plain
+ * bytes > cap, *out_len = the size needed, nothing decoded); per-entry failures are in
+ * entries[k].status only.  Host synchronisations: the index's 3 plus the extraction's.
+ *
+ * dmx_zip_index / dmx_inflate_zip: the same on host buffers; the archive is staged with one copy to
+ * the device, the device form runs there, the bytes are copied back with one copy.
+ *
+ * The calls take the context mutex, are ordered against the context's other deflate / inflate work
+ * like dmx_inflate_bgzf_device, run on `stream` (NULL: the context's stream; the host forms always
+ * there) and return after their last host synchronisation.  A context with n_gpus > 1 runs them on
+ * its first device.
+ *
+ * Not covered: writing archives, encryption, methods other than 0 and 8, multi-disk archives, a
+ * ZIP64 end record with extensible data (it is looked for directly in front of its locator),
+ * comparing local with central names, graph capture. */
+typedef struct dmx_zip_entry {      /* 64 bytes */
+    uint64_t name_off;   /* the name's first byte in the archive (inside the central directory) */
+    uint64_t data_off;   /* the entry's first data byte */
+    uint64_t csize, usize;
+    uint64_t uoffset;    /* its first byte in a full extraction: prefix sum of usize */
+    uint32_t crc;
+    uint32_t dostime;    /* time | date << 16 */
+    uint16_t name_len, method, gpflags, reserved;
+    int32_t  status;     /* DMX_OK, or why this entry cannot be extracted */
+    uint32_t path;       /* after extraction: 6, the single-stream path, 0 for stored */
+} dmx_zip_entry;
+int dmx_zip_index_device(dmx_ctx* ctx, const void* d_in, size_t n, dmx_zip_entry* entries, size_t entry_cap,
+                         size_t* count, uint64_t* plain_bytes, void* stream);
+int dmx_zip_extract_device(dmx_ctx* ctx, const void* d_in, size_t n, const dmx_zip_entry* entries, size_t count,
+                           const size_t* sel, size_t nsel, uint32_t flags, void* d_out, size_t cap,
+                           dmx_batch_result* res, size_t* out_len, void* stream);
+int dmx_inflate_zip_device(dmx_ctx* ctx, const void* d_in, size_t n, uint32_t flags, void* d_out, size_t cap,
+                           dmx_zip_entry* entries, size_t entry_cap, size_t* count, size_t* out_len, void* stream);
+int dmx_zip_index(dmx_ctx* ctx, const uint8_t* in, size_t n, dmx_zip_entry* entries, size_t entry_cap,
+                  size_t* count, uint64_t* plain_bytes);
+int dmx_inflate_zip(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t* out, size_t cap,
+                    dmx_zip_entry* entries, size_t entry_cap, size_t* count, size_t* out_len);
+
 /* ---- seek index and ranged reads for unblocked streams (zran's idea; not in the reference) -----
  * BGZF is blocked for random access; an ordinary zlib / gzip / pigz stream and libdmx's own output
  * are not.  These calls build a zran-style index while a stream is decoded once -- checkpoints at
