@@ -16,7 +16,8 @@
 //              that does not fit (bt_close)
 // Inflate: the streams the batch kernel keeps, listed longest class first (class = floor(log2 n)):
 // a histogram of the classes, the classes' first positions, a scatter (bt_mark, bt_class,
-// bt_class_starts).
+// bt_class_starts; under hipcc also the scatter's one device form, bt_order_scatter, which
+// k_bt_order and the ZIP extraction's k_zip_order call).
 #pragma once
 #include <stdint.h>
 
@@ -154,5 +155,33 @@ DMX_HD inline uint32_t bt_class_starts(const uint32_t* hist, uint32_t* start) {
     }
     return run;
 }
+
+#if defined(__HIPCC__)
+// The order list's scatter (k_bt_order, zip_dir.hip's k_zip_order), called by every thread of a
+// workgroup of at least kBatchClasses threads: stream i of class cls goes into the list where
+// `keep`.  The classes' first positions (every workgroup scans the 64 counts of hist itself), the
+// stream's rank among the workgroup's of its class, the workgroup's range of each class claimed
+// from cursor (kBatchClasses words, zero at the launch).  Thread 0 returns the kept streams of
+// the whole launch.
+__device__ __forceinline__ uint32_t bt_order_scatter(bool keep, uint32_t cls, uint32_t i, const uint32_t* hist,
+                                                     uint32_t* cursor, uint32_t* order) {
+    __shared__ uint32_t start[kBatchClasses];  // the class's first position in the order list
+    __shared__ uint32_t h[kBatchClasses];      // this workgroup's streams per class, then their base
+    uint32_t kept = 0;
+    if (threadIdx.x < kBatchClasses) h[threadIdx.x] = 0;
+    if (threadIdx.x == 0) kept = bt_class_starts(hist, start);
+    __syncthreads();
+    uint32_t rank = 0;
+    if (keep) rank = atomicAdd(&h[cls], 1u);
+    __syncthreads();
+    if (threadIdx.x < kBatchClasses) {
+        const uint32_t mine = h[threadIdx.x];
+        h[threadIdx.x] = mine ? atomicAdd(&cursor[threadIdx.x], mine) : 0u;
+    }
+    __syncthreads();
+    if (keep) order[start[cls] + h[cls] + rank] = i;
+    return kept;
+}
+#endif
 
 }  // namespace dmx

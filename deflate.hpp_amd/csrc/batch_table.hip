@@ -10,8 +10,8 @@
 //                 count
 //   k_bt_desc     one lane per stream: its InflateBatchDesc, the result of a stream that is not
 //                 decoded here, the class histogram (LDS per workgroup, then one atomic per class)
-//   k_bt_order    the classes' first positions (every workgroup scans the 64 counts itself) and
-//                 the scatter of the kept streams into the order list
+//   k_bt_order    the scatter of the kept streams into the order list (bt_order_scatter,
+//                 batch_table.h, which the ZIP extraction's k_zip_order calls too)
 // Counts and flags are written with ordinary (vector) stores from one lane.
 #include "dmx_internal.h"
 
@@ -78,31 +78,16 @@ __global__ __launch_bounds__(BT_NT) void k_bt_desc(const uint8_t* const* in, con
 __global__ __launch_bounds__(BT_NT) void k_bt_order(const InflateBatchDesc* desc, uint64_t count, uint64_t max_n,
                                                     uint64_t route_bytes, const uint32_t* hist, uint32_t* cursor,
                                                     uint32_t* order, uint32_t* norder) {
-    __shared__ uint32_t start[kBatchClasses];  // the class's first position in the order list
-    __shared__ uint32_t h[kBatchClasses];      // this workgroup's streams per class, then their base
-    if (threadIdx.x < kBatchClasses) h[threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        const uint32_t kept = bt_class_starts(hist, start);
-        if (blockIdx.x == 0) *norder = kept;
-    }
-    __syncthreads();
     const uint64_t i = (uint64_t)blockIdx.x * BT_NT + threadIdx.x;
     bool keep = false;
-    uint32_t cls = 0, rank = 0;
+    uint32_t cls = 0;
     if (i < count) {
         const InflateBatchDesc d = desc[i];
         keep = bt_mark(d.n, max_n, route_bytes != 0, route_bytes, d.out != nullptr) == BT_KEEP;
         cls = bt_class(d.n);
-        if (keep) rank = atomicAdd(&h[cls], 1u);
     }
-    __syncthreads();
-    // the workgroup's range in each class it holds streams of
-    if (threadIdx.x < kBatchClasses) {
-        const uint32_t mine = h[threadIdx.x];
-        h[threadIdx.x] = mine ? atomicAdd(&cursor[threadIdx.x], mine) : 0u;
-    }
-    __syncthreads();
-    if (keep) order[start[cls] + h[cls] + rank] = (uint32_t)i;
+    const uint32_t kept = bt_order_scatter(keep, cls, (uint32_t)i, hist, cursor, order);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *norder = kept;
 }
 
 hipError_t launch_batch_segtab(const uint8_t* const* in, const uint64_t* n, uint64_t count, uint64_t max_n,

@@ -4,120 +4,36 @@
 //
 // A BGZF file is a linked list through 16-bit BSIZE fields.  The steps are bgzf_chain.h's (plain
 // C++, run serially by tests/cpp/bgzf_chain_test.cpp):
-//   k_bgzf_count / k_bgzf_list   every offset that starts with 1f 8b 08 + FEXTRA is tested with
-//                                bgzf_next; per-tile counts, launch_scan_u32, then the candidates
-//                                in offset order.  The list is sized by the count, which the host
-//                                reads in between: a payload of fake headers cannot overflow it.
+//   k_scan_count / k_scan_list   cand_scan.h's scan over BgzfScan: every offset that starts with
+//                                1f 8b 08 + FEXTRA is tested with bgzf_next
 //   k_bgzf_link                  successor = the candidate at off + size (binary search)
-//   k_bgzf_double                level k -> level k + 1, once per level
+//   k_bgzf_double                level k -> level k + 1, once per level (launch_chain_links runs
+//                                both, for the ZIP directory's records too)
 //   k_bgzf_head                  one thread: members reachable from offset 0, chain status
 //   k_bgzf_rank                  member r = r hops from candidate 0, along the bits of r
 //   launch_scan_u32              uoff = exclusive prefix sum of ISIZE, total plain bytes
 // False candidates inside payloads take part in the links and the doubling, but only what is
 // reachable from candidate 0 at offset 0 is ever counted or ranked.
+// k_member_status is the file status of every decode of a member list (BGZF, multi-member gzip).
 //
-// Every store is a plain vector store.  No byte at or beyond in + n is read; the 16-byte staging
-// loads start at the 16-byte boundary below `in` and bytes outside [in, in + n) are zeroed.
+// Every store is a plain vector store.  No byte at or beyond in + n is read, but by the scan's
+// staging (cand_scan.h).
 #include "bgzf_chain.h"
-#include "dmx_device.h"
-#include "dmx_internal.h"
+#include "cand_scan.h"
 
 namespace dmx {
 
 constexpr uint32_t BC_NT = 256;
-constexpr uint32_t BC_TILE = BC_NT * 16;  // staged bytes per workgroup (16 per thread)
 
-// Stages tile `tile` of the 16-byte aligned view of the file (plus 16 bytes of the next tile) and
-// tests this thread's 16 offsets: bit j of the result = a member starts at aligned position
-// tile * BC_TILE + 16 * t + j.  Ends past a barrier; lds holds BC_TILE / 4 + 4 words.
-__device__ __forceinline__ uint32_t bc_tile_mask(const uint8_t* in, uint64_t n, uint64_t tile, uint32_t* lds) {
-    const uint32_t t = threadIdx.x;
-    const uint64_t lead = (uintptr_t)in & 15, vend = lead + n;
-    const uint8_t* vbase = in - lead;
-    // (an aligned 16-byte load at q < vend shares its 16-byte line with a byte of the file)
-    auto load = [&](uint64_t q, uint32_t* dst) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q < vend) v = *reinterpret_cast<const uint4*>(vbase + q);
-        uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        if (q < lead || q + 16 > vend) {  // the ragged ends
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                uint32_t m = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const uint64_t p = q + 4 * k + b;
-                    if (p >= lead && p < vend) m |= 0xFFu << (8 * b);
-                }
-                w[k] &= m;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) dst[k] = w[k];
-    };
-    const uint64_t p0 = tile * BC_TILE + 16ull * t;
-    load(p0, lds + 4 * t);
-    if (t == 0) load(tile * BC_TILE + BC_TILE, lds + BC_TILE / 4);
-    __syncthreads();
-    uint32_t w[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) w[k] = lds[4 * t + k];
-    uint32_t mask = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const uint32_t word = __builtin_amdgcn_alignbyte(w[(j >> 2) + 1], w[j >> 2], j & 3);
-        const uint64_t p = p0 + j;
-        if (bgzf_magic(word) && p >= lead && p + 18 <= vend) {  // (fewer than 18 bytes: no member)
-            BgzfCand c;
-            if (bgzf_candidate(in, n, p - lead, &c)) mask |= 1u << j;
-        }
-    }
-    __syncthreads();
-    return mask;
-}
-
-// the workgroup's exclusive scan of `v` (result) and its sum (*total); sm holds BC_NT / 64 words
-__device__ __forceinline__ uint32_t bc_block_scan(uint32_t v, uint32_t* sm, uint32_t* total) {
-    const uint32_t t = threadIdx.x;
-    const uint32_t inc = wave_incl_scan(v);
-    if ((t & 63) == 63) sm[t >> 6] = inc;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < BC_NT / 64; k++) {
-        if (k < (t >> 6)) before += sm[k];
-        sum += sm[k];
-    }
-    *total = sum;
-    return before + inc - v;
-}
-
-__global__ __launch_bounds__(BC_NT) void k_bgzf_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[BC_TILE / 4 + 4];
-    __shared__ uint32_t sm[BC_NT / 64];
-    const uint32_t mask = bc_tile_mask(in, n, blockIdx.x, lds);
-    uint32_t total;
-    (void)bc_block_scan(__popc(mask), sm, &total);
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
-}
-
-// cands holds ncand entries (the count the host read): nothing is written past them
-__global__ __launch_bounds__(BC_NT) void k_bgzf_list(const uint8_t* in, uint64_t n, const uint64_t* tile_offs,
-                                                     BgzfCand* cands, uint64_t ncand) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[BC_TILE / 4 + 4];
-    __shared__ uint32_t sm[BC_NT / 64];
-    uint32_t mask = bc_tile_mask(in, n, blockIdx.x, lds);
-    uint32_t total;
-    uint64_t at = tile_offs[blockIdx.x] + bc_block_scan(__popc(mask), sm, &total);
-    const uint64_t lead = (uintptr_t)in & 15;
-    const uint64_t p0 = (uint64_t)blockIdx.x * BC_TILE + 16ull * threadIdx.x;
-    while (mask) {
-        const int j = __ffs(mask) - 1;
-        mask &= mask - 1;
-        BgzfCand c;
-        if (bgzf_candidate(in, n, p0 + j - lead, &c) && at < ncand) cands[at] = c;
-        at++;
-    }
-}
+// the candidate scan's format (cand_scan.h): a member is what bgzf_next accepts
+struct BgzfScan {
+    const uint8_t* in;
+    uint64_t n;
+    using Cand = BgzfCand;
+    static constexpr uint32_t kMinBytes = 18;
+    __device__ bool magic(uint32_t word) const { return bgzf_magic(word); }
+    __device__ bool candidate(uint64_t off, BgzfCand* c) const { return bgzf_candidate(in, n, off, c); }
+};
 
 __global__ __launch_bounds__(BC_NT) void k_bgzf_link(const BgzfCand* cands, uint64_t ncand, uint64_t n, uint32_t* J) {
     const uint64_t i = (uint64_t)blockIdx.x * BC_NT + threadIdx.x;
@@ -213,15 +129,15 @@ __global__ __launch_bounds__(BC_NT) void k_bgzf_range_copy(const ::dmx_bgzf_entr
         out[p - u0] = src[p - a];
 }
 
-// The file status of dmx_inflate_bgzf: the first member whose result is not DMX_OK, with
-// DMX_ERR_CAPACITY or a decoded size other than ISIZE (desc[k].cap) read as DMX_ERR_CHECKSUM.
+// The status of a file of members: the first member whose result is not DMX_OK, with
+// DMX_ERR_CAPACITY or a decoded size other than the one expected (desc[k].cap) read as `mismatch`.
 // *key (preset to all ones) = min over the failing members of index << 32 | status.
-__global__ __launch_bounds__(BC_NT) void k_bgzf_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc,
-                                                       uint64_t members, unsigned long long* key) {
+__global__ __launch_bounds__(BC_NT) void k_member_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc,
+                                                         uint64_t members, int mismatch, unsigned long long* key) {
     const uint64_t k = (uint64_t)blockIdx.x * BC_NT + threadIdx.x;
     if (k >= members) return;
     int st = res[k].status;
-    if (st == DMX_ERR_CAPACITY || (st == DMX_OK && res[k].bytes != desc[k].cap)) st = DMX_ERR_CHECKSUM;
+    if (st == DMX_ERR_CAPACITY || (st == DMX_OK && res[k].bytes != desc[k].cap)) st = mismatch;
     if (st != DMX_OK) atomicMin(key, (unsigned long long)((k << 32) | (uint32_t)st));
 }
 
@@ -279,37 +195,33 @@ __global__ __launch_bounds__(BC_NT) void k_bgzf_pack(const uint8_t* slots, uint6
 // ---- launches -----------------------------------------------------------------------------------
 static uint32_t bc_grid(uint64_t count) { return (uint32_t)((count + BC_NT - 1) / BC_NT); }
 
-uint64_t bgzf_tiles(const uint8_t* in, uint64_t n) {
-    return n ? (((uintptr_t)in & 15) + n + BC_TILE - 1) / BC_TILE : 0;
-}
-
 hipError_t launch_bgzf_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts, uint64_t* tile_offs,
                              uint64_t* ncand, hipStream_t st) {
-    const uint64_t nt = bgzf_tiles(in, n);
-    if (!nt) return hipSuccess;
-    hipLaunchKernelGGL(k_bgzf_count, dim3((uint32_t)nt), dim3(BC_NT), 0, st, in, n, tile_counts);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_scan_u32(tile_counts, tile_offs, nt, ncand, st);
+    return launch_scan_count(BgzfScan{in, n}, in, n, tile_counts, tile_offs, ncand, st);
+}
+
+hipError_t launch_chain_links(const BgzfCand* cands, uint64_t ncand, uint64_t end, uint32_t* J, hipStream_t st) {
+    if (!ncand) return hipSuccess;
+    hipLaunchKernelGGL(k_bgzf_link, dim3(bc_grid(ncand)), dim3(BC_NT), 0, st, cands, ncand, end, J);
+    for (uint32_t k = 0; k + 1 < bgzf_levels(ncand); k++)
+        hipLaunchKernelGGL(k_bgzf_double, dim3(bc_grid(ncand)), dim3(BC_NT), 0, st, J + (uint64_t)k * ncand,
+                           J + (uint64_t)(k + 1) * ncand, ncand);
+    return hipGetLastError();
 }
 
 hipError_t launch_bgzf_chain(const uint8_t* in, uint64_t n, const uint64_t* tile_offs, uint64_t ncand,
                              BgzfCand* cands, uint32_t* J, BgzfCand* rows, uint32_t* isz, uint64_t* uoff,
                              BgzfChainHead* head, hipStream_t st) {
     const uint32_t levels = bgzf_levels(ncand);
-    if (ncand) {
-        hipLaunchKernelGGL(k_bgzf_list, dim3((uint32_t)bgzf_tiles(in, n)), dim3(BC_NT), 0, st, in, n, tile_offs, cands,
-                           ncand);
-        hipLaunchKernelGGL(k_bgzf_link, dim3(bc_grid(ncand)), dim3(BC_NT), 0, st, cands, ncand, n, J);
-        for (uint32_t k = 0; k + 1 < levels; k++)
-            hipLaunchKernelGGL(k_bgzf_double, dim3(bc_grid(ncand)), dim3(BC_NT), 0, st, J + (uint64_t)k * ncand,
-                               J + (uint64_t)(k + 1) * ncand, ncand);
-    }
+    hipError_t e = launch_scan_list(BgzfScan{in, n}, in, n, tile_offs, cands, ncand, st);
+    if (e != hipSuccess) return e;
+    e = launch_chain_links(cands, ncand, n, J, st);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_bgzf_head, dim3(1), dim3(64), 0, st, in, n, cands, ncand, J, levels, head);
     if (ncand)
         hipLaunchKernelGGL(k_bgzf_rank, dim3(bc_grid(ncand)), dim3(BC_NT), 0, st, cands, ncand, J, levels, head, rows,
                            isz);
-    const hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
     // (ncand == 0: the scan of nothing writes the total 0)
     return launch_scan_u32(isz, uoff, ncand, &head->total, st);
@@ -344,10 +256,11 @@ hipError_t launch_bgzf_range_copy(const ::dmx_bgzf_entry* idx, uint64_t count, u
     return hipGetLastError();
 }
 
-hipError_t launch_bgzf_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
-                              unsigned long long* key, hipStream_t st) {
+hipError_t launch_member_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
+                                int mismatch_status, unsigned long long* key, hipStream_t st) {
     if (!members) return hipSuccess;
-    hipLaunchKernelGGL(k_bgzf_status, dim3(bc_grid(members)), dim3(BC_NT), 0, st, res, desc, members, key);
+    hipLaunchKernelGGL(k_member_status, dim3(bc_grid(members)), dim3(BC_NT), 0, st, res, desc, members,
+                       mismatch_status, key);
     return hipGetLastError();
 }
 

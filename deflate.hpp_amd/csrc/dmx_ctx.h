@@ -17,6 +17,7 @@
 
 #include "../../include/dmx.h"
 #include "dmx_internal.h"
+#include "cand_scan.h"
 #include "inflate_plan.h"
 
 namespace dmx {
@@ -218,6 +219,35 @@ struct CallGuard {
 inline size_t up16(size_t b) { return (b + 15) & ~size_t(15); }
 // the batch deflate knows 16 and 32 KiB segments (64 KiB blocks pair front segments)
 inline bool has_batch_deflate(const dmx_ctx* c) { return c->seg == 16384 || c->seg == 32768; }
+
+// The candidate scans' scratch in c->bgzt (cand_scan.h; BGZF, multi-member gzip, ZIP):
+//   tile counts | tile offsets | the candidate count | `extra` bytes of the caller's small words
+// carve sizes it for `tiles` tiles; count takes the result of the launch_*_count over counts, offs
+// and d_ncand, reads the count back -- one host synchronisation -- and refuses `limit` candidates
+// or more with DMX_ERR_NOMEM (candidate indices are 32-bit).
+struct ScanScratch {
+    uint32_t* counts = nullptr;
+    uint64_t* offs = nullptr;
+    uint64_t* d_ncand = nullptr;
+    uint8_t* words = nullptr;
+    uint64_t ncand = 0;
+    bool carve(dmx_ctx* c, uint64_t tiles, size_t extra) {
+        const size_t off_offs = up16(tiles * 4), off_ncand = off_offs + up16(scan_words(tiles) * 8);
+        if (!c->bgzt.ensure(off_ncand + 16 + extra)) return false;
+        uint8_t* const tb = c->bgzt.as<uint8_t>();
+        counts = reinterpret_cast<uint32_t*>(tb);
+        offs = reinterpret_cast<uint64_t*>(tb + off_offs);
+        d_ncand = reinterpret_cast<uint64_t*>(tb + off_ncand);
+        words = tb + off_ncand + 16;
+        return true;
+    }
+    int count(hipError_t launched, uint64_t limit, hipStream_t st) {
+        HIPCHK(launched);
+        HIPCHK(hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return ncand >= limit ? DMX_ERR_NOMEM : DMX_OK;
+    }
+};
 
 // dmx_host.cpp
 // The deflate's scratch for nseg segments, of which the front kernel sees nfront of fseg_bytes

@@ -342,12 +342,14 @@ struct BgzfChainHead {
                        // or the first failing member's status
     uint32_t pad_;
 };
-// tiles of the candidate scan (0 for n == 0); tile_counts holds as many words, tile_offs
-// scan_words(tiles) entries
-uint64_t bgzf_tiles(const uint8_t* in, uint64_t n);
+// The candidate scans (launch_bgzf_count, launch_gzm_count, launch_zip_count) are cand_scan.h's:
+// tile_counts holds scan_tiles(region) words, tile_offs scan_words(tiles) entries.
 // *ncand = the offsets of in[0, n) where bgzf_next succeeds (n > 0)
 hipError_t launch_bgzf_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts, uint64_t* tile_offs,
                              uint64_t* ncand, hipStream_t st);
+// The jump tables of a chain of records [off, off + size) that must end at `end`: J = bgzf_levels(ncand)
+// * ncand words, level 0 by bgzf_link, each further one by bgzf_double (BGZF members, ZIP central records)
+hipError_t launch_chain_links(const BgzfCand* cands, uint64_t ncand, uint64_t end, uint32_t* J, hipStream_t st);
 // The member table for the ncand the host read back: rows[r] (r < head->members) in chain order,
 // uoff = the exclusive prefix sum of their ISIZE, *head.  cands / rows / isz: ncand entries, J:
 // bgzf_levels(ncand) * ncand words, uoff: scan_words(ncand) entries.  ncand == 0 (and n == 0):
@@ -370,9 +372,11 @@ hipError_t launch_bgzf_range_desc(const uint8_t* in, const ::dmx_bgzf_entry* idx
 hipError_t launch_bgzf_range_copy(const ::dmx_bgzf_entry* idx, uint64_t count, uint64_t u0, uint64_t u1,
                                   const uint8_t* edge, uint8_t* out, hipStream_t st);
 // *key (preset to all ones by the caller) = min over the members whose result is not DMX_OK of
-// index << 32 | (uint32_t)status, with dmx_inflate_bgzf's mapping to DMX_ERR_CHECKSUM
-hipError_t launch_bgzf_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
-                              unsigned long long* key, hipStream_t st);
+// index << 32 | (uint32_t)status.  DMX_ERR_CAPACITY or a decoded size other than desc[k].cap is
+// mismatch_status: DMX_ERR_CHECKSUM for BGZF (dmx_inflate_bgzf's mapping; cap is ISIZE),
+// DMX_ERR_INTERNAL for multi-member gzip (cap is the size the measuring pass found)
+hipError_t launch_member_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
+                                int mismatch_status, unsigned long long* key, hipStream_t st);
 // deflate: member i (res[i].bytes at slots + i * stride) to out + the prefix sum, then the EOF
 // member; *head as above.  Nothing is written to out unless every member is DMX_OK and the file
 // fits cap.  sizes: count words, offs: scan_words(count) entries, *key preset to all ones.
@@ -382,9 +386,7 @@ hipError_t launch_bgzf_pack(const uint8_t* slots, uint64_t stride, const ::dmx_b
 
 
 // multi-member gzip files in device memory (gzip_members.hip; the walk: gzip_members.h).
-// tiles of the candidate scan (0 for n == 0) and a tile's bytes; tile_counts holds as many words,
-// tile_offs scan_words(tiles) entries
-uint64_t gzm_tiles(const uint8_t* in, uint64_t n);
+// a tile's bytes of the candidate scan
 uint32_t gzm_tile_bytes();
 // *ncand = the offsets of in[0, n) where 1f 8b 08 starts a header that gzip_head_len accepts (n > 0)
 hipError_t launch_gzm_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts, uint64_t* tile_offs,
@@ -404,19 +406,11 @@ hipError_t launch_gzm_measure(const uint8_t* in, uint64_t n, const GzmCand* cand
 // status of a header there}.  *flag: a scratch word.
 hipError_t launch_gzm_gaps(const uint8_t* in, uint64_t n, const GzmGap* gaps, uint64_t ngaps, uint64_t longest,
                            uint64_t forced, unsigned long long* flag, uint64_t* res, hipStream_t st);
-// *key (preset to all ones by the caller) = min over the members whose result is not DMX_OK of
-// index << 32 | (uint32_t)status; a decoded size other than desc[k].cap, the size the measuring
-// pass found, is DMX_ERR_INTERNAL
-hipError_t launch_gzm_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
-                             unsigned long long* key, hipStream_t st);
 
 // ZIP archives in device memory (zip_dir.hip; the steps: zip_dir.h).
 // *head = the end record of in[0, n), n >= 22: directory region, count, base; status DMX_ERR_DATA
 // where there is none or it spans disks
 hipError_t launch_zip_tail(const uint8_t* in, uint64_t n, ZipHead* head, hipStream_t st);
-// tiles of the candidate scan over a region (0 for len == 0); tile_counts holds as many words,
-// tile_offs scan_words(tiles) entries
-uint64_t zip_tiles(const uint8_t* reg, uint64_t len);
 // *ncand = the offsets of h's directory region where a central record starts (h.dir_size > 0)
 hipError_t launch_zip_count(const uint8_t* in, const ZipHead& h, uint32_t* tile_counts, uint64_t* tile_offs,
                             uint64_t* ncand, hipStream_t st);

@@ -3,11 +3,10 @@
 //
 // RFC 1952 2.2: a gzip file is a series of members.  Member k + 1 starts where member k's DEFLATE
 // stream and trailer end, and nothing in a header says where that is -- only a decode does.  So:
-//   k_gzm_count / k_gzm_write   every offset p of the file is tested: 1f 8b 08 and a header that
-//                               parses with 8 bytes left behind it (gzip_head_len,
-//                               container_parse.h) is a CANDIDATE {p, header length}.  Per-tile
-//                               counts, launch_scan_u32, then the candidates in offset order; the
-//                               list is sized by the count, which the host reads in between.
+//   k_scan_count / k_scan_list  cand_scan.h's scan over GzmScan: every offset p of the file is
+//                               tested: 1f 8b 08 and a header that parses with 8 bytes left behind
+//                               it (gzip_head_len, container_parse.h) is a CANDIDATE {p, header
+//                               length}.
 //   k_gzm_measure               one wavefront per candidate on a persistent grid: inflate_blocks
 //                               over the candidate's stream with a sink that only counts, over a
 //                               window of at most `limit` bytes -> GzmRec {end, plain bytes,
@@ -28,109 +27,26 @@
 //
 // Every store is a plain vector store; there is no inline assembly.  No byte at or beyond in + n
 // is read, but for the aligned loads that share their 4- or 16-byte line with a byte of the file
-// (as in bgzf_chain.hip and the batch decoder's input ring).
+// (the scan's staging, cand_scan.h, and the batch decoder's input ring).
 #include "inflate_common.h"
+#include "cand_scan.h"
 
 namespace dmx {
 
 constexpr uint32_t GM_NT = 256;
-constexpr uint32_t GM_TILE = GM_NT * 16;  // staged bytes per workgroup (16 per thread)
 
-// Stages tile `tile` of the 16-byte aligned view of the file (plus 16 bytes of the next tile) and
-// tests this thread's 16 offsets: bit j of the result = a candidate starts at aligned position
-// tile * GM_TILE + 16 * t + j.  The magic comes from the staged bytes; the header parse reads the
-// file itself, past the tile's edge where the header goes there.  Ends past a barrier; lds holds
-// GM_TILE / 4 + 4 words.  (The staging is bgzf_chain.hip's, which is not touched.)
-__device__ __forceinline__ uint32_t gm_tile_mask(const uint8_t* in, uint64_t n, uint64_t tile, uint32_t* lds) {
-    const uint32_t t = threadIdx.x;
-    const uint64_t lead = (uintptr_t)in & 15, vend = lead + n;
-    const uint8_t* vbase = in - lead;
-    // (an aligned 16-byte load at q < vend shares its 16-byte line with a byte of the file)
-    auto load = [&](uint64_t q, uint32_t* dst) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q < vend) v = *reinterpret_cast<const uint4*>(vbase + q);
-        uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        if (q < lead || q + 16 > vend) {  // the ragged ends
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                uint32_t m = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const uint64_t p = q + 4 * k + b;
-                    if (p >= lead && p < vend) m |= 0xFFu << (8 * b);
-                }
-                w[k] &= m;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) dst[k] = w[k];
-    };
-    const uint64_t p0 = tile * GM_TILE + 16ull * t;
-    load(p0, lds + 4 * t);
-    if (t == 0) load(tile * GM_TILE + GM_TILE, lds + GM_TILE / 4);
-    __syncthreads();
-    uint32_t w[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) w[k] = lds[4 * t + k];
-    uint32_t mask = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const uint32_t word = __builtin_amdgcn_alignbyte(w[(j >> 2) + 1], w[j >> 2], j & 3);
-        const uint64_t p = p0 + j;
-        if ((word & 0xFFFFFFu) == 0x088B1Fu && p >= lead && p + 18 <= vend) {  // (fewer than 18 bytes: no member)
-            uint64_t head;
-            if (gzip_head_len(in + (p - lead), n - (p - lead), &head) == DMX_OK) mask |= 1u << j;
-        }
+// the candidate scan's format (cand_scan.h): 1f 8b 08 and a header that gzip_head_len accepts
+struct GzmScan {
+    const uint8_t* in;
+    uint64_t n;
+    using Cand = GzmCand;
+    static constexpr uint32_t kMinBytes = 18;
+    __device__ bool magic(uint32_t word) const { return (word & 0xFFFFFFu) == 0x088B1Fu; }
+    __device__ bool candidate(uint64_t off, GzmCand* c) const {
+        c->off = off;
+        return gzip_head_len(in + off, n - off, &c->head) == DMX_OK;
     }
-    __syncthreads();
-    return mask;
-}
-
-// the workgroup's exclusive scan of `v` (result) and its sum (*total); sm holds GM_NT / 64 words
-__device__ __forceinline__ uint32_t gm_block_scan(uint32_t v, uint32_t* sm, uint32_t* total) {
-    const uint32_t t = threadIdx.x;
-    const uint32_t inc = wave_incl_scan(v);
-    if ((t & 63) == 63) sm[t >> 6] = inc;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < GM_NT / 64; k++) {
-        if (k < (t >> 6)) before += sm[k];
-        sum += sm[k];
-    }
-    *total = sum;
-    return before + inc - v;
-}
-
-__global__ __launch_bounds__(GM_NT) void k_gzm_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[GM_TILE / 4 + 4];
-    __shared__ uint32_t sm[GM_NT / 64];
-    const uint32_t mask = gm_tile_mask(in, n, blockIdx.x, lds);
-    uint32_t total;
-    (void)gm_block_scan(__popc(mask), sm, &total);
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
-}
-
-// cands holds ncand entries (the count the host read): nothing is written past them
-__global__ __launch_bounds__(GM_NT) void k_gzm_write(const uint8_t* in, uint64_t n, const uint64_t* tile_offs,
-                                                     GzmCand* cands, uint64_t ncand) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[GM_TILE / 4 + 4];
-    __shared__ uint32_t sm[GM_NT / 64];
-    uint32_t mask = gm_tile_mask(in, n, blockIdx.x, lds);
-    uint32_t total;
-    uint64_t at = tile_offs[blockIdx.x] + gm_block_scan(__popc(mask), sm, &total);
-    const uint64_t lead = (uintptr_t)in & 15;
-    const uint64_t p0 = (uint64_t)blockIdx.x * GM_TILE + 16ull * threadIdx.x;
-    while (mask) {
-        const int j = __ffs(mask) - 1;
-        mask &= mask - 1;
-        const uint64_t p = p0 + j - lead;
-        GzmCand c;
-        c.off = p;
-        if (gzip_head_len(in + p, n - p, &c.head) == DMX_OK && at < ncand) cands[at] = c;
-        at++;
-    }
-}
+};
 
 // ---- the measuring pass -------------------------------------------------------------------------
 constexpr uint32_t GM_RW = 512, GM_RC = 128;  // input ring words, words per slide (the batch decoder's)
@@ -247,40 +163,17 @@ __global__ void k_gzm_gap_status(const uint8_t* in, uint64_t n, const unsigned l
     res[1] = (uint64_t)(int64_t)st;
 }
 
-// The file status: *key (preset to all ones) = min over the failing members of index << 32 | status.
-// desc[k].cap is the size the measuring pass found for member k.
-__global__ __launch_bounds__(GM_NT) void k_gzm_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc,
-                                                      uint64_t members, unsigned long long* key) {
-    const uint64_t k = (uint64_t)blockIdx.x * GM_NT + threadIdx.x;
-    if (k >= members) return;
-    int st = res[k].status;
-    // the decode and the measuring pass disagree on a member's size: the layout is broken
-    if (st == DMX_ERR_CAPACITY || (st == DMX_OK && res[k].bytes != desc[k].cap)) st = DMX_ERR_INTERNAL;
-    if (st != DMX_OK) atomicMin(key, (unsigned long long)((k << 32) | (uint32_t)st));
-}
-
 // ---- launches -----------------------------------------------------------------------------------
-uint64_t gzm_tiles(const uint8_t* in, uint64_t n) {
-    return n ? (((uintptr_t)in & 15) + n + GM_TILE - 1) / GM_TILE : 0;
-}
-uint32_t gzm_tile_bytes() { return GM_TILE; }
+uint32_t gzm_tile_bytes() { return kScanTile; }
 
 hipError_t launch_gzm_count(const uint8_t* in, uint64_t n, uint32_t* tile_counts, uint64_t* tile_offs,
                             uint64_t* ncand, hipStream_t st) {
-    const uint64_t nt = gzm_tiles(in, n);
-    if (!nt) return hipSuccess;
-    hipLaunchKernelGGL(k_gzm_count, dim3((uint32_t)nt), dim3(GM_NT), 0, st, in, n, tile_counts);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_scan_u32(tile_counts, tile_offs, nt, ncand, st);
+    return launch_scan_count(GzmScan{in, n}, in, n, tile_counts, tile_offs, ncand, st);
 }
 
 hipError_t launch_gzm_write(const uint8_t* in, uint64_t n, const uint64_t* tile_offs, GzmCand* cands,
                             uint64_t ncand, hipStream_t st) {
-    if (!ncand) return hipSuccess;
-    hipLaunchKernelGGL(k_gzm_write, dim3((uint32_t)gzm_tiles(in, n)), dim3(GM_NT), 0, st, in, n, tile_offs, cands,
-                       ncand);
-    return hipGetLastError();
+    return launch_scan_list(GzmScan{in, n}, in, n, tile_offs, cands, ncand, st);
 }
 
 hipError_t launch_gzm_measure(const uint8_t* in, uint64_t n, const GzmCand* cands, uint64_t ncand, GzmRec* recs,
@@ -311,14 +204,6 @@ hipError_t launch_gzm_gaps(const uint8_t* in, uint64_t n, const GzmGap* gaps, ui
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_gzm_gap_status, dim3(1), dim3(64), 0, st, in, n, flag, forced, res);
-    return hipGetLastError();
-}
-
-hipError_t launch_gzm_status(const ::dmx_batch_result* res, const InflateBatchDesc* desc, uint64_t members,
-                             unsigned long long* key, hipStream_t st) {
-    if (!members) return hipSuccess;
-    hipLaunchKernelGGL(k_gzm_status, dim3((uint32_t)((members + GM_NT - 1) / GM_NT)), dim3(GM_NT), 0, st, res, desc,
-                       members, key);
     return hipGetLastError();
 }
 

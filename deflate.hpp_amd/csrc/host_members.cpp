@@ -56,18 +56,13 @@ struct BgzfChain {
 };
 int bgzf_chain_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, hipStream_t st, BgzfChain* ch) {
     if (!n) return DMX_OK;  // no member, DMX_OK
-    const uint64_t nt = bgzf_tiles(d_in, n);
-    const size_t off_offs = up16(nt * 4), off_head = off_offs + up16(scan_words(nt) * 8);
-    if (!c->bgzt.ensure(off_head + 64)) return DMX_ERR_NOMEM;
-    uint8_t* const tb = c->bgzt.as<uint8_t>();
-    uint64_t* const tile_offs = reinterpret_cast<uint64_t*>(tb + off_offs);
-    ch->head = reinterpret_cast<BgzfChainHead*>(tb + off_head);
-    uint64_t* const d_ncand = reinterpret_cast<uint64_t*>(tb + off_head + 32);
-    HIPCHK(launch_bgzf_count(d_in, n, reinterpret_cast<uint32_t*>(tb), tile_offs, d_ncand, st));
-    uint64_t ncand = 0;
-    HIPCHK(hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ncand >= kBgzfNone) return DMX_ERR_NOMEM;  // (links are 32-bit candidate indices)
+    ScanScratch S;
+    if (!S.carve(c, scan_tiles(d_in, n), sizeof(BgzfChainHead))) return DMX_ERR_NOMEM;
+    ch->head = reinterpret_cast<BgzfChainHead*>(S.words);
+    // (links are 32-bit candidate indices)
+    const int rc = S.count(launch_bgzf_count(d_in, n, S.counts, S.offs, S.d_ncand, st), kBgzfNone, st);
+    if (rc != DMX_OK) return rc;
+    const uint64_t ncand = S.ncand;
     const uint32_t levels = bgzf_levels(ncand);
     const size_t off_rows = up16(ncand * sizeof(BgzfCand)), off_J = off_rows * 2;
     const size_t off_isz = off_J + up16((size_t)levels * ncand * 4), off_uoff = off_isz + up16(ncand * 4);
@@ -75,7 +70,7 @@ int bgzf_chain_locked(dmx_ctx* c, const uint8_t* d_in, size_t n, hipStream_t st,
     uint8_t* const cb = c->bgzc.as<uint8_t>();
     ch->rows = reinterpret_cast<BgzfCand*>(cb + off_rows);
     ch->uoff = reinterpret_cast<uint64_t*>(cb + off_uoff);
-    HIPCHK(launch_bgzf_chain(d_in, n, tile_offs, ncand, reinterpret_cast<BgzfCand*>(cb),
+    HIPCHK(launch_bgzf_chain(d_in, n, S.offs, ncand, reinterpret_cast<BgzfCand*>(cb),
                              reinterpret_cast<uint32_t*>(cb + off_J), ch->rows,
                              reinterpret_cast<uint32_t*>(cb + off_isz), ch->uoff, ch->head, st));
     BgzfChainHead h{};
@@ -120,8 +115,8 @@ MemberTab member_tab(uint8_t* base, size_t count) {
 // The framed batch inflate over arrays that are already on the device: `build` fills T.desc and
 // T.order with `count` members (path 6 throughout: every member is below kBatchRouteBytes),
 // `after` may add a launch behind the decode.  One host synchronisation, the read-back of *key:
-// all ones, or index << 32 | (uint32_t)status of the first member that failed (launch_bgzf_status,
-// launch_gzm_status).  main_events: dmx_stats.ms_main_kernel brackets the decode kernel.
+// all ones, or index << 32 | (uint32_t)status of the first member that failed 
+// (launch_member_status).  main_events: dmx_stats.ms_main_kernel brackets the decode kernel.
 template <class Build, class After>
 int members_decode_locked(dmx_ctx* c, const MemberTab& T, size_t count, uint32_t format, bool verify,
                           bool main_events, hipStream_t st, Build build, After after, unsigned long long* key) {
@@ -134,7 +129,9 @@ int members_decode_locked(dmx_ctx* c, const MemberTab& T, size_t count, uint32_t
     if (main_events) (void)hipEventRecord(c->ev[2], st);
     if (verify) HIPCHK(launch_checksum_batch(T.desc, T.res, T.side, count, true, T.ticket + 4, st));
     HIPCHK(launch_frame_verdict(T.side, T.res, count, format, verify, st));
-    HIPCHK((format == DMX_FRAME_GZIP ? launch_gzm_status : launch_bgzf_status)(T.res, T.desc, count, T.key, st));
+    // (a size other than the expected one: BGZF's ISIZE is wrong; gzip's measuring pass and decode disagree)
+    HIPCHK(launch_member_status(T.res, T.desc, count, format == DMX_FRAME_GZIP ? DMX_ERR_INTERNAL : DMX_ERR_CHECKSUM,
+                                T.key, st));
     HIPCHK(after());
     HIPCHK(hipEventRecord(c->ev_inf, st));
     c->inf_pending = true;
@@ -179,7 +176,7 @@ struct GzmCall {
     size_t cap;
     int phase;  // gzm_main_phase
     hipStream_t st;
-    // c->bgzt's small words: candidate count | gap flag | gap result (2) | measuring ticket
+    // c->bgzt's small words (ScanScratch::words): gap flag | gap result (2) | at 32 the measuring ticket
     uint8_t* d_words = nullptr;
     float phase_ms = 0;  // phase < 2: the events' time, read before a long member's own call records them anew
     std::vector<GzmCand> hc;
@@ -196,27 +193,22 @@ struct GzmCall {
 // Phase 1: the candidates and their records, measured on the device and read back
 int gzm_measure(dmx_ctx* c, GzmCall& G) {
     const hipStream_t st = G.st;
-    const uint64_t nt = gzm_tiles(G.in, G.n);
-    const size_t off_offs = up16(nt * 4), off_words = off_offs + up16(scan_words(nt) * 8);
-    if (!c->bgzt.ensure(off_words + 128)) return DMX_ERR_NOMEM;
-    uint8_t* const tb = c->bgzt.as<uint8_t>();
-    uint64_t* const tile_offs = reinterpret_cast<uint64_t*>(tb + off_offs);
-    G.d_words = tb + off_words;
-    uint64_t* const d_ncand = reinterpret_cast<uint64_t*>(G.d_words);
+    ScanScratch S;
+    if (!S.carve(c, scan_tiles(G.in, G.n), 48)) return DMX_ERR_NOMEM;
+    G.d_words = S.words;
     unsigned int* const d_mticket = reinterpret_cast<unsigned int*>(G.d_words + 32);
     if (G.phase == 0) (void)hipEventRecord(c->ev[1], st);
-    HIPCHK(launch_gzm_count(G.in, G.n, reinterpret_cast<uint32_t*>(tb), tile_offs, d_ncand, st));
-    uint64_t ncand = 0;
-    HIPCHK(hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ncand >= 0xFFFFFFFFull) return DMX_ERR_NOMEM;  // (tickets and order entries are 32-bit)
+    // (tickets and order entries are 32-bit)
+    const int rc = S.count(launch_gzm_count(G.in, G.n, S.counts, S.offs, S.d_ncand, st), 0xFFFFFFFFull, st);
+    if (rc != DMX_OK) return rc;
+    const uint64_t ncand = S.ncand;
     G.hc.resize(ncand);
     G.hr.resize(ncand);
     const size_t off_recs = up16(ncand * sizeof(GzmCand));
     if (!c->bgzc.ensure(off_recs + ncand * sizeof(GzmRec) + 16)) return DMX_ERR_NOMEM;
     GzmCand* const d_cands = c->bgzc.as<GzmCand>();
     GzmRec* const d_recs = reinterpret_cast<GzmRec*>(c->bgzc.as<uint8_t>() + off_recs);
-    HIPCHK(launch_gzm_write(G.in, G.n, tile_offs, d_cands, ncand, st));
+    HIPCHK(launch_gzm_write(G.in, G.n, S.offs, d_cands, ncand, st));
     if (G.phase == 0) (void)hipEventRecord(c->ev[2], st);
     if (G.phase == 1) (void)hipEventRecord(c->ev[1], st);
     int occupancy = 0;
@@ -308,8 +300,8 @@ int gzm_walk_chain(dmx_ctx* c, GzmCall& G) {
 int gzm_check_gaps(dmx_ctx* c, GzmCall& G) {
     if (!G.bad_start && G.gaps.empty()) return DMX_OK;
     const hipStream_t st = G.st;
-    unsigned long long* const d_flag = reinterpret_cast<unsigned long long*>(G.d_words + 8);
-    uint64_t* const d_gapres = reinterpret_cast<uint64_t*>(G.d_words + 16);
+    unsigned long long* const d_flag = reinterpret_cast<unsigned long long*>(G.d_words);
+    uint64_t* const d_gapres = reinterpret_cast<uint64_t*>(G.d_words + 8);
     uint64_t longest = 0;
     for (const GzmGap& g : G.gaps) longest = std::max(longest, g.b - g.a);
     GzmGap* d_gaps = nullptr;

@@ -26,13 +26,9 @@ struct ZipIndex {
 int zip_index_locked(dmx_ctx* c, const uint8_t* in, size_t n, dmx_zip_entry* entries, size_t entry_cap, hipStream_t st,
                      ZipIndex* X) {
     // (a directory is shorter than the archive: the tile arrays are sized before its extent is known)
-    const uint64_t nt_max = zip_tiles(nullptr, n + 16);
-    const size_t off_counts = 64, off_offs = off_counts + up16(nt_max * 4);
-    if (!c->bgzt.ensure(off_offs + scan_words(nt_max) * 8)) return DMX_ERR_NOMEM;
-    uint8_t* const tb = c->bgzt.as<uint8_t>();
-    ZipHead* const d_head = reinterpret_cast<ZipHead*>(tb);
-    uint64_t* const d_ncand = reinterpret_cast<uint64_t*>(tb + 48);
-    uint64_t* const tile_offs = reinterpret_cast<uint64_t*>(tb + off_offs);
+    ScanScratch S;
+    if (!S.carve(c, scan_tiles(nullptr, n + 16), sizeof(ZipHead))) return DMX_ERR_NOMEM;
+    ZipHead* const d_head = reinterpret_cast<ZipHead*>(S.words);
     HIPCHK(launch_zip_tail(in, n, d_head, st));
     ZipHead& h = X->h;
     HIPCHK(hipMemcpyAsync(&h, d_head, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -42,11 +38,10 @@ int zip_index_locked(dmx_ctx* c, const uint8_t* in, size_t n, dmx_zip_entry* ent
         if (h.count) h.status = DMX_ERR_DATA;
         return DMX_OK;
     }
-    HIPCHK(launch_zip_count(in, h, reinterpret_cast<uint32_t*>(tb + off_counts), tile_offs, d_ncand, st));
-    uint64_t ncand = 0;
-    HIPCHK(hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ncand >= kBgzfNone) return DMX_ERR_NOMEM;  // (links are 32-bit candidate indices)
+    // (links are 32-bit candidate indices)
+    const int rc = S.count(launch_zip_count(in, h, S.counts, S.offs, S.d_ncand, st), kBgzfNone, st);
+    if (rc != DMX_OK) return rc;
+    const uint64_t ncand = S.ncand;
     if (!ncand || h.count > ncand) {               // (a chain is no longer than the candidate list)
         h.status = DMX_ERR_DATA;
         return DMX_OK;
@@ -61,7 +56,7 @@ int zip_index_locked(dmx_ctx* c, const uint8_t* in, size_t n, dmx_zip_entry* ent
     uint8_t* const cb = c->bgzc.as<uint8_t>();
     X->d_ents = reinterpret_cast<dmx_zip_entry*>(cb + off_ents);
     ZipHead* const d_head2 = reinterpret_cast<ZipHead*>(cb + off_tot + 16);
-    HIPCHK(launch_zip_chain(in, n, h, tile_offs, ncand, reinterpret_cast<BgzfCand*>(cb),
+    HIPCHK(launch_zip_chain(in, n, h, S.offs, ncand, reinterpret_cast<BgzfCand*>(cb),
                             reinterpret_cast<uint32_t*>(cb + off_J), X->d_ents, reinterpret_cast<uint32_t*>(cb + off_lo),
                             reinterpret_cast<uint32_t*>(cb + off_hi), reinterpret_cast<uint64_t*>(cb + off_slo),
                             reinterpret_cast<uint64_t*>(cb + off_shi), reinterpret_cast<uint64_t*>(cb + off_tot),

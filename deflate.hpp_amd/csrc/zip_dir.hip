@@ -7,11 +7,10 @@
 //   k_zip_tail                  the highest valid end record position in the last 65557 bytes
 //                               (one workgroup, an LDS maximum), then one thread reads the ZIP64
 //                               records and writes the head
-//   k_zip_count / k_zip_list    every offset of the directory region that starts with 50 4b 01 02
-//                               is tested with zip_cd_candidate; per-tile counts, launch_scan_u32,
-//                               then the candidates in offset order.  The list is sized by the
-//                               count, which the host reads in between.
-//   k_zip_link / k_zip_double   successor = the candidate at off + size; level k -> level k + 1
+//   k_scan_count / k_scan_list  cand_scan.h's scan over ZipScan: every offset of the directory
+//                               region that starts with 50 4b 01 02 is tested with zip_cd_candidate
+//   launch_chain_links          bgzf_chain.hip's: successor = the candidate at off + size; level k
+//                               -> level k + 1
 //   k_zip_head                  one thread: the chain from the region's first byte must end at its
 //                               end after as many records as the end record states
 //   k_zip_entries               one thread per entry: rank lookup, the record's fields, the local
@@ -30,16 +29,14 @@
 // only what is reachable from the candidate at the directory's first byte is counted or ranked.
 //
 // Every store is a plain vector store.  No byte outside [in, in + n) is read but for the 16-byte
-// aligned loads that share their line with a byte of the archive; the staged bytes outside the
-// directory region are zeroed.
+// aligned loads that share their line with a byte of the archive: the scan's staging (cand_scan.h)
+// and k_zip_copy's source lines.
 #include "zip_dir.h"
-#include "dmx_device.h"
-#include "dmx_internal.h"
+#include "cand_scan.h"
 
 namespace dmx {
 
 constexpr uint32_t ZD_NT = 256;
-constexpr uint32_t ZD_TILE = ZD_NT * 16;  // staged bytes per workgroup (16 per thread)
 constexpr uint32_t ZD_TAIL_NT = 1024;
 
 // ---- the end record -----------------------------------------------------------------------------
@@ -60,112 +57,16 @@ __global__ __launch_bounds__(ZD_TAIL_NT) void k_zip_tail(const uint8_t* in, uint
     }
 }
 
-// ---- the candidate scan over the directory region [d0, d1) ------------------------------------
-// Stages tile `tile` of the 16-byte aligned view of the region (plus 16 bytes of the next tile) and
-// tests this thread's 16 offsets: bit j of the result = a record starts at aligned position
-// tile * ZD_TILE + 16 * t + j.  Ends past a barrier; lds holds ZD_TILE / 4 + 4 words.
-__device__ __forceinline__ uint32_t zd_tile_mask(const uint8_t* in, uint64_t d0, uint64_t d1, uint64_t tile,
-                                                 uint32_t* lds) {
-    const uint32_t t = threadIdx.x;
-    const uint8_t* const reg = in + d0;
-    const uint64_t lead = (uintptr_t)reg & 15, vend = lead + (d1 - d0);
-    const uint8_t* vbase = reg - lead;
-    // (an aligned 16-byte load at q < vend shares its 16-byte line with a byte of the region)
-    auto load = [&](uint64_t q, uint32_t* dst) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q < vend) v = *reinterpret_cast<const uint4*>(vbase + q);
-        uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        if (q < lead || q + 16 > vend) {  // the ragged ends
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                uint32_t m = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const uint64_t p = q + 4 * k + b;
-                    if (p >= lead && p < vend) m |= 0xFFu << (8 * b);
-                }
-                w[k] &= m;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) dst[k] = w[k];
-    };
-    const uint64_t p0 = tile * ZD_TILE + 16ull * t;
-    load(p0, lds + 4 * t);
-    if (t == 0) load(tile * ZD_TILE + ZD_TILE, lds + ZD_TILE / 4);
-    __syncthreads();
-    uint32_t w[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) w[k] = lds[4 * t + k];
-    uint32_t mask = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const uint32_t word = __builtin_amdgcn_alignbyte(w[(j >> 2) + 1], w[j >> 2], j & 3);
-        const uint64_t p = p0 + j;
-        if (word == kZipSigCentral && p >= lead && p + 46 <= vend) {  // (fewer than 46 bytes: no record)
-            BgzfCand c;
-            if (zip_cd_candidate(in, d0, d1, d0 + (p - lead), &c)) mask |= 1u << j;
-        }
-    }
-    __syncthreads();
-    return mask;
-}
-
-// the workgroup's exclusive scan of `v` (result) and its sum (*total); sm holds ZD_NT / 64 words
-__device__ __forceinline__ uint32_t zd_block_scan(uint32_t v, uint32_t* sm, uint32_t* total) {
-    const uint32_t t = threadIdx.x;
-    const uint32_t inc = wave_incl_scan(v);
-    if ((t & 63) == 63) sm[t >> 6] = inc;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < ZD_NT / 64; k++) {
-        if (k < (t >> 6)) before += sm[k];
-        sum += sm[k];
-    }
-    *total = sum;
-    return before + inc - v;
-}
-
-__global__ __launch_bounds__(ZD_NT) void k_zip_count(const uint8_t* in, uint64_t d0, uint64_t d1,
-                                                     uint32_t* tile_counts) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[ZD_TILE / 4 + 4];
-    __shared__ uint32_t sm[ZD_NT / 64];
-    const uint32_t mask = zd_tile_mask(in, d0, d1, blockIdx.x, lds);
-    uint32_t total;
-    (void)zd_block_scan(__popc(mask), sm, &total);
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
-}
-
-// cands holds ncand entries (the count the host read): nothing is written past them
-__global__ __launch_bounds__(ZD_NT) void k_zip_list(const uint8_t* in, uint64_t d0, uint64_t d1,
-                                                    const uint64_t* tile_offs, BgzfCand* cands, uint64_t ncand) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[ZD_TILE / 4 + 4];
-    __shared__ uint32_t sm[ZD_NT / 64];
-    uint32_t mask = zd_tile_mask(in, d0, d1, blockIdx.x, lds);
-    uint32_t total;
-    uint64_t at = tile_offs[blockIdx.x] + zd_block_scan(__popc(mask), sm, &total);
-    const uint64_t lead = (uintptr_t)(in + d0) & 15;
-    const uint64_t p0 = (uint64_t)blockIdx.x * ZD_TILE + 16ull * threadIdx.x;
-    while (mask) {
-        const int j = __ffs(mask) - 1;
-        mask &= mask - 1;
-        BgzfCand c;
-        if (zip_cd_candidate(in, d0, d1, d0 + (p0 + j - lead), &c) && at < ncand) cands[at] = c;
-        at++;
-    }
-}
-
-// ---- the chain ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(ZD_NT) void k_zip_link(const BgzfCand* cands, uint64_t ncand, uint64_t d1, uint32_t* J) {
-    const uint64_t i = (uint64_t)blockIdx.x * ZD_NT + threadIdx.x;
-    if (i < ncand) J[i] = bgzf_link(cands, ncand, i, d1);
-}
-
-__global__ __launch_bounds__(ZD_NT) void k_zip_double(const uint32_t* Jk, uint32_t* Jn, uint64_t ncand) {
-    const uint64_t i = (uint64_t)blockIdx.x * ZD_NT + threadIdx.x;
-    if (i < ncand) Jn[i] = bgzf_double(Jk, i);
-}
+// ---- the candidate scan over the directory region [d0, d1) and the chain -----------------------
+// the scan's format (cand_scan.h): a central record that lies inside the region
+struct ZipScan {
+    const uint8_t* in;
+    uint64_t d0, d1;
+    using Cand = BgzfCand;
+    static constexpr uint32_t kMinBytes = 46;
+    __device__ bool magic(uint32_t word) const { return word == kZipSigCentral; }
+    __device__ bool candidate(uint64_t off, BgzfCand* c) const { return zip_cd_candidate(in, d0, d1, d0 + off, c); }
+};
 
 __global__ void k_zip_head(const BgzfCand* cands, uint64_t ncand, const uint32_t* J, uint32_t levels, ZipHead h,
                            ZipHead* head) {
@@ -245,26 +146,9 @@ __global__ __launch_bounds__(ZD_NT) void k_zip_jobs(const ::dmx_zip_entry* ents,
 // cursor: kBatchClasses words, zero at the launch (k_bt_order's scatter, over the job kinds)
 __global__ __launch_bounds__(ZD_NT) void k_zip_order(const InflateBatchDesc* desc, const uint32_t* kind, uint64_t count,
                                                      const uint32_t* hist, uint32_t* cursor, uint32_t* order) {
-    __shared__ uint32_t start[kBatchClasses];
-    __shared__ uint32_t h[kBatchClasses];
-    if (threadIdx.x < kBatchClasses) h[threadIdx.x] = 0;
-    if (threadIdx.x == 0) (void)bt_class_starts(hist, start);
-    __syncthreads();
     const uint64_t i = (uint64_t)blockIdx.x * ZD_NT + threadIdx.x;
-    bool keep = false;
-    uint32_t cls = 0, rank = 0;
-    if (i < count) {
-        keep = kind[i] == ZIP_JOB_BATCH;
-        cls = bt_class(desc[i].n);
-        if (keep) rank = atomicAdd(&h[cls], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < kBatchClasses) {
-        const uint32_t mine = h[threadIdx.x];
-        h[threadIdx.x] = mine ? atomicAdd(&cursor[threadIdx.x], mine) : 0u;
-    }
-    __syncthreads();
-    if (keep) order[start[cls] + h[cls] + rank] = (uint32_t)i;
+    const bool keep = i < count && kind[i] == ZIP_JOB_BATCH;
+    (void)bt_order_scatter(keep, keep ? bt_class(desc[i].n) : 0u, (uint32_t)i, hist, cursor, order);
 }
 
 // Workgroup k copies stored entry k: desc[k].n bytes from desc[k].in to desc[k].out, any alignment
@@ -330,10 +214,6 @@ __global__ __launch_bounds__(ZD_NT) void k_zip_verdict(const ::dmx_zip_entry* en
 // ---- launches -----------------------------------------------------------------------------------
 static uint32_t zd_grid(uint64_t count) { return (uint32_t)((count + ZD_NT - 1) / ZD_NT); }
 
-uint64_t zip_tiles(const uint8_t* reg, uint64_t len) {
-    return len ? (((uintptr_t)reg & 15) + len + ZD_TILE - 1) / ZD_TILE : 0;
-}
-
 hipError_t launch_zip_tail(const uint8_t* in, uint64_t n, ZipHead* head, hipStream_t st) {
     hipLaunchKernelGGL(k_zip_tail, dim3(1), dim3(ZD_TAIL_NT), 0, st, in, n, head);
     return hipGetLastError();
@@ -341,13 +221,9 @@ hipError_t launch_zip_tail(const uint8_t* in, uint64_t n, ZipHead* head, hipStre
 
 hipError_t launch_zip_count(const uint8_t* in, const ZipHead& h, uint32_t* tile_counts, uint64_t* tile_offs,
                             uint64_t* ncand, hipStream_t st) {
-    const uint64_t nt = zip_tiles(in + h.dir_off, h.dir_size);
-    if (!nt) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_zip_count, dim3((uint32_t)nt), dim3(ZD_NT), 0, st, in, h.dir_off, h.dir_off + h.dir_size,
-                       tile_counts);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_scan_u32(tile_counts, tile_offs, nt, ncand, st);
+    if (!h.dir_size) return hipErrorInvalidValue;
+    return launch_scan_count(ZipScan{in, h.dir_off, h.dir_off + h.dir_size}, in + h.dir_off, h.dir_size, tile_counts,
+                             tile_offs, ncand, st);
 }
 
 hipError_t launch_zip_chain(const uint8_t* in, uint64_t n, const ZipHead& h, const uint64_t* tile_offs, uint64_t ncand,
@@ -356,17 +232,15 @@ hipError_t launch_zip_chain(const uint8_t* in, uint64_t n, const ZipHead& h, con
     if (!ncand || h.count > ncand) return hipErrorInvalidValue;
     const uint64_t d1 = h.dir_off + h.dir_size;
     const uint32_t levels = bgzf_levels(ncand);
-    hipLaunchKernelGGL(k_zip_list, dim3((uint32_t)zip_tiles(in + h.dir_off, h.dir_size)), dim3(ZD_NT), 0, st, in,
-                       h.dir_off, d1, tile_offs, cands, ncand);
-    hipLaunchKernelGGL(k_zip_link, dim3(zd_grid(ncand)), dim3(ZD_NT), 0, st, cands, ncand, d1, J);
-    for (uint32_t k = 0; k + 1 < levels; k++)
-        hipLaunchKernelGGL(k_zip_double, dim3(zd_grid(ncand)), dim3(ZD_NT), 0, st, J + (uint64_t)k * ncand,
-                           J + (uint64_t)(k + 1) * ncand, ncand);
+    hipError_t e = launch_scan_list(ZipScan{in, h.dir_off, d1}, in + h.dir_off, h.dir_size, tile_offs, cands, ncand, st);
+    if (e != hipSuccess) return e;
+    e = launch_chain_links(cands, ncand, d1, J, st);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_zip_head, dim3(1), dim3(64), 0, st, cands, ncand, J, levels, h, head);
     if (h.count)
         hipLaunchKernelGGL(k_zip_entries, dim3(zd_grid(h.count)), dim3(ZD_NT), 0, st, in, n, h.base, h.count, cands,
                            ncand, J, levels, head, ents, lo, hi);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
     // (count == 0: the scans of nothing write the totals 0)
     e = launch_scan_u32(lo, off_lo, h.count, totals, st);

@@ -6,6 +6,8 @@
 // length, rank, end of chain) are run serially over all "threads" on a heap copy of exactly n
 // bytes, so a read at or beyond n is a sanitizer report; the member table and the status are
 // compared with the serial walk `for (off = 0; off < n;) bgzf_next(...)` of dmx_inflate_bgzf.
+// Also the plain C++ of the candidate scan's staging (cand_scan.h): which bytes of an aligned
+// 16-byte line lie in the scanned region, for every misalignment and every short length.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "../../deflate.hpp_amd/csrc/bgzf_chain.h"
+#include "../../deflate.hpp_amd/csrc/cand_scan.h"
 
 using namespace dmx;
 typedef std::vector<uint8_t> Bytes;
@@ -172,7 +175,38 @@ static Bytes fake_headers(size_t payload) {
     return f;
 }
 
+// cand_scan.h's ragged-end rule against its bytewise definition: the region is [lead, lead + len) of
+// the aligned view; every line the staging can load (and one past), every byte of it
+static void line_masks() {
+    for (uint64_t lead = 0; lead < 16; lead++)
+        for (uint64_t len = 0; len <= 48; len++) {
+            const uint64_t vend = lead + len;
+            for (uint64_t q = 0; q <= vend + 16; q += 16) {
+                uint32_t m[4];
+                scan_line_mask(q, lead, vend, m);
+                bool all = true;
+                for (uint64_t j = 0; j < 16; j++) {
+                    const bool in = q + j >= lead && q + j < vend;
+                    all = all && in;
+                    const uint32_t got = (m[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+                    CHECK(got == (in ? 0xFFu : 0u), "line mask: lead %llu len %llu line %llu byte %llu: %02x",
+                          (unsigned long long)lead, (unsigned long long)len, (unsigned long long)q,
+                          (unsigned long long)j, got);
+                }
+                CHECK(scan_line_inside(q, lead, vend) == all, "line inside: lead %llu len %llu line %llu",
+                      (unsigned long long)lead, (unsigned long long)len, (unsigned long long)q);
+            }
+            // the tiles cover the view: the last one holds its last byte
+            const uint8_t* const reg = reinterpret_cast<const uint8_t*>((uintptr_t)(4096 + lead));
+            CHECK(scan_tiles(reg, len) == (len ? 1u : 0u), "tiles: lead %llu len %llu", (unsigned long long)lead,
+                  (unsigned long long)len);
+        }
+    const uint8_t* const r5 = reinterpret_cast<const uint8_t*>((uintptr_t)(4096 + 5));
+    CHECK(scan_tiles(r5, kScanTile - 5) == 1 && scan_tiles(r5, kScanTile - 4) == 2, "tiles: the edge");
+}
+
 int main() {
+    line_masks();
     // three members: every truncation, every single-byte change of the first 64 bytes and of
     // each member's BSIZE / ISIZE bytes
     const Bytes m0 = member(pattern(200, 1)), m1 = member(pattern(77, 2)), m2 = member(pattern(130, 3));

@@ -194,6 +194,29 @@ def test_empty_files(ctx):
         assert st == dmx.DMX_OK and got == b"" and canaries_ok(h, ooff, 0)
 
 
+TILE = 4096  # the candidate scan's tile (csrc/cand_scan.h)
+
+
+def test_tile_edge_members(ctx):
+    """The second of three members starts 0-3 bytes before and behind a multiple of the scan's tile
+    in the 16-byte aligned view of the file, whose first byte sits at `mod` in that view."""
+    src = dmx.corpus("text", 2 * TILE + 400, offset=17)
+    second, third = member(src[:300]), member(src[300:340])
+    for mod in (0, 5):
+        for edge in (TILE, 2 * TILE):
+            for delta in range(-3, 4):
+                start = edge + delta - mod  # the first member's size
+                first = member(src[340:340 + start - 31], stored=True)  # header 18, stored block 5, trailer 8
+                assert len(first) == start
+                f = first + second + third
+                want = walk(f)
+                assert want[1, 0] == start
+                assert np.array_equal(index_dev(ctx, f, mod=mod), want), (mod, edge, delta)
+                st, got, h, ooff = inflate_dev(ctx, f, mod=mod)
+                assert st == dmx.DMX_OK and got == gzip.decompress(f), (mod, edge, delta)
+                assert canaries_ok(h, ooff, len(got)), (mod, edge, delta)
+
+
 # ---- hostile candidates ----------------------------------------------------------------------------
 def stored_again(inner, block=BLOCK):
     return b"".join(member(inner[o:o + block], stored=True) for o in range(0, len(inner), block)) + EOF_BLOCK

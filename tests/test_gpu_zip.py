@@ -124,6 +124,38 @@ def test_index_alone(ctx, name):
     assert plain == plain_size(archive)
 
 
+TILE = 4096  # the candidate scan's tile (csrc/cand_scan.h)
+
+
+def test_tile_edge_records(ctx):
+    """A central record's signature starts 0-3 bytes before and behind a multiple of the scan's tile
+    in the 16-byte aligned view of the directory region.  160 stored entries with 10-byte names give
+    a directory of two tiles and a bit; the first entry's name length picks the record that lands
+    there and its payload's length the region's place in the view."""
+    count = 160
+    for mod in (0, 5):
+        for edge in (TILE, 2 * TILE):
+            for delta in range(-3, 4):
+                target = edge + delta
+                # local entry: 30 + name + payload; central record: 46 + name
+                pick = [(nl, pl) for nl in range(1, 57) for pl in range(1, 17)
+                        if (target - (mod + 30 + nl + pl + (count - 1) * 41) % 16 - 46 - nl) % 56 == 0]
+                nl, pl = pick[0]
+                archive = zc.write_zip([("n" * nl, b"p" * pl, 0)] +
+                                       [("e%09d" % k, b"x", 0) for k in range(1, count)])
+                with zipfile.ZipFile(io.BytesIO(archive)) as z:
+                    sizes = [46 + len(zi.orig_filename.encode()) + len(zi.extra) + len(zi.comment)
+                             for zi in z.infolist()]
+                    at = (mod + z.start_dir) % 16  # the region's first byte in its aligned view
+                    starts = [at + sum(sizes[:k]) for k in range(count)]
+                assert target in starts[1:] and starts[-1] + sizes[-1] > 2 * TILE, (mod, edge, delta)
+                t, off = dev(archive, mod)
+                entries, plain = ctx.zip_index_device(t.data_ptr() + off, len(archive))
+                assert host_of(t) == host_of(dev(archive, mod)[0])
+                check_against_zipfile(archive, entries, None)
+                assert plain == plain_size(archive)
+
+
 def test_mixed_archive_has_the_shapes():
     """stored entries of 0, 1, 15, 16, 17 and 4097 bytes, a deflated empty entry (03 00), a directory"""
     archive = zc.mixed()
