@@ -346,8 +346,9 @@ struct DfSmem : DfBufs<SEG, df_early(SEG)> {
     uint32_t tokmap[SEG / 32];  // token-start bitmap (parse walk; chunks share boundary words)
     uint16_t lasttok[NWALK + 1];  // last token start of each parse chunk
     uint32_t scan[4 * DF_NT / 64];
-    uint32_t sh[64];  // 43: backward mismatch tag, 44: run candidate, 45 / 47: terminal run,
-                      // 46: mismatch tag, 48..62: divisor-period tags
+    uint32_t sh[64];  // 43: backward mismatch tag, 44: run candidate, 45 / 47: terminal run (47:
+                      // its distance | first match bit << 16), 46: mismatch tag, 48..62:
+                      // divisor-period tags
 };
 static_assert(sizeof(DfSmem<32768>) <= 160 * 1024, "the front kernel's LDS fits a CU's 160 KiB");
 
@@ -543,6 +544,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
     // in it the compiler spills its kernel arguments to scratch)
     constexpr bool TERMRUN = !L3 && SEG >= 32768;
     constexpr uint32_t RUN_NONE = 0xFFFFFFFFu;
+    // (a run segment's leading literals are not walked: see the match bitmap and the walk)
+    constexpr bool LITPREFIX = TERMRUN;
     DMX_PHASE(A.dbg, seg, 0);
 
     // ---- load the segment into LDS (16 B per lane when aligned) ------------------------
@@ -594,6 +597,8 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // the first word compared; RUN_NONE without a terminal run.
         [[maybe_unused]] uint32_t run_e = RUN_NONE;
         [[maybe_unused]] float run_rcp = 0.f;  // 1 / run_d (known_len's multiple test)
+        // A run segment's first match bit at or above D, at most nb (uniform; see the bitmap)
+        [[maybe_unused]] uint32_t run_fm = 0;
         // ---- match candidates: rounds of 2*DF_NT positions, two per thread ---------------
         if (level >= 2) {
             // Table entries carry a fingerprint of the 4-byte key (product bits below the hash
@@ -671,6 +676,96 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     if (SKIP && pend) dlr = S.sh[44];
                     const uint32_t i0 = p0 >> 2, sh = p0 & 3;  // sh = 0 or 2
                     const uint32_t wa = data32[i0], wb = data32[i0 + 1];
+                    // The run test of a round at distance dl: leaves the tested distance in skip_d
+                    // and the first mismatch in sh[46] (read behind the caller's barrier).
+                    auto run_test = [&](uint32_t dl) {
+                        // Periodic data: the trigger's candidate is a first occurrence in an
+                        // earlier round, often a multiple of the period.  The largest k <= 16
+                        // (dl % k == 0) whose dl / k repeats the 256 bytes at r0 gives the
+                        // tested distance (64 threads per k, one word each; a mismatch tags
+                        // sh[48 + k - 2] with the round); the test below then verifies it.
+                        {
+                            const uint32_t ki = (uint32_t)t >> 6, k = ki + 2, bq = r0 + 4 * ((uint32_t)t & 63);
+                            if (ki < 15 && dl % k == 0 && bq + 4 <= nb) {
+                                const uint32_t dk = dl / k, ia = (bq - dk) >> 2, sk = (bq - dk) & 3;
+                                if (data32[bq >> 2] != __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sk))
+                                    atomicMax(&S.sh[48 + ki], rr + 1);
+                            }
+                        }
+                        __syncthreads();  // (uniform: dl and wait are the same in every wave)
+                        uint32_t dsel = dl;
+#pragma unroll
+                        for (uint32_t k = 2; k <= 16; k++)
+                            dsel = (dl % k == 0 && S.sh[48 + k - 2] != rr + 1) ? dl / k : dsel;
+                        dl = __builtin_amdgcn_readfirstlane(dsel);
+                        // words r0 / 4 + t + 1024 j (neighbouring lanes, neighbouring words:
+                        // no bank conflicts) against the words dl bytes before them
+                        skip_d = dl;
+                        const uint32_t sa = (r0 - dl) & 3;  // (r0 is a multiple of 4)
+                        uint32_t mm = 0xFFFFFFFFu;
+#pragma unroll
+                        for (int j = 7; j >= 0; j--) {
+                            const uint32_t bq = r0 + 4 * ((uint32_t)t + DF_NT * j);
+                            if (bq < nb) {
+                                const uint32_t ia = (bq - dl) >> 2;
+                                const uint32_t df = data32[bq >> 2] ^
+                                                    __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sa);
+                                mm = df ? bq + ((uint32_t)__builtin_ctz(df) >> 3) : mm;
+                            }
+                        }
+                        if (mm != 0xFFFFFFFFu) atomicMax(&S.sh[46], ((rr + 1) << 16) | (0xFFFFu - mm));
+                    };
+                    // the end of the positions whose key the test verified at skip_d: p < m - 3
+                    // (m: first mismatch)
+                    auto tested_end = [&]() -> uint32_t {
+                        const uint32_t mt = __builtin_amdgcn_readfirstlane(S.sh[46]);
+                        const uint32_t m = (mt >> 16) == rr + 1 ? 0xFFFFu - (mt & 0xFFFFu) : 0xFFFFFFFFu;
+                        return m >= nb ? nb : (m >= 3 ? m - 3 : 0u);
+                    };
+                    // Test first (32 KiB, level 2): a round that tests does so before any of its
+                    // table work, behind a barrier of its own.  A terminal run ends the rounds
+                    // with no key computed and no atomic issued (the table is never read again);
+                    // a round inside a run that ends later issues only the previous round's
+                    // latest-occurrence updates, which later rounds read (its own first
+                    // occurrences carry this round's tag, and this round looks nothing up); a
+                    // failed test goes on to the whole round below.
+                    constexpr bool TESTFIRST = TERMRUN && SKIP;
+                    if (TESTFIRST && pend) {
+                        pend = false;
+                        const uint32_t dl = __builtin_amdgcn_readfirstlane(dlr);
+                        wait -= wait ? 1u : 0u;
+                        if (!wait && dl) {
+                            run_test(dl);
+                            __syncthreads();
+                            skip_end = tested_end();
+                            if (skip_end >= nb) {  // a terminal run: the rounds end here
+                                if (t == 0) {      // (see run_lo)
+                                    S.sh[45] = r0;
+                                    // (upper half: the first match bit, none yet -- see the bitmap)
+                                    S.sh[47] = skip_d | (LITPREFIX ? 0xFFFF0000u : 0u);
+                                }
+                                skipped = true;
+                                return;
+                            }
+                            if (r0 + RP <= skip_end) {  // this round is inside the run
+                                // (the previous round's latest occurrences, as below)
+                                const uint32_t hn = (uint32_t)__builtin_amdgcn_update_dpp((int)NOH, (int)(prev.ok0 ? prev.h0 : NOH), 0x101, 0xF, 0xF, false);
+                                if (prev.ok0 && prev.h0 != (prev.ok1 ? prev.h1 : NOH))
+                                    atomicMax(&U[2 * prev.h0], ((prev.p0 + 1) << 16) | prev.f0);
+                                if (prev.ok1 && prev.h1 != hn) atomicMax(&U[2 * prev.h1], ((prev.p0 + 2) << 16) | prev.f1);
+                                if (FULL || p0 < nb)
+                                    cand32[p0 >> 1] = (FULL || p0 + 4 <= nb ? skip_d : 0u) |
+                                                      ((FULL || p1 + 4 <= nb ? skip_d : 0u) << 16);
+                                cur = RoundState{NOH, NOH, p0, 0, 0, false, false};
+                                backoff = 1;
+                                skipped = true;
+                                return;
+                            }
+                            skip_d = 0;
+                            wait = backoff;
+                            backoff = min(2 * backoff, 16u);
+                        }
+                    }
                     const uint32_t k0 = __builtin_amdgcn_alignbyte(wb, wa, sh);
                     const uint32_t k1 = __builtin_amdgcn_alignbyte(wb, wa, sh + 1);
                     const uint32_t prod0 = k0 * 0x1E35A7BDu;
@@ -695,64 +790,19 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         atomicMax(&U[2 * prev.h0], ((prev.p0 + 1) << 16) | prev.f0);
                     if (prev.ok1 && prev.h1 != hn) atomicMax(&U[2 * prev.h1], ((prev.p0 + 2) << 16) | prev.f1);
                     bool tested = false;
-                    if (SKIP && pend) {
+                    if (!TESTFIRST && SKIP && pend) {
                         pend = false;
-                        uint32_t dl = __builtin_amdgcn_readfirstlane(dlr);
+                        const uint32_t dl = __builtin_amdgcn_readfirstlane(dlr);
                         wait -= wait ? 1u : 0u;
                         if (!wait && dl) {
                             tested = true;
-                            // Periodic data: the trigger's candidate is a first occurrence in an
-                            // earlier round, often a multiple of the period.  The largest k <= 16
-                            // (dl % k == 0) whose dl / k repeats the 256 bytes at r0 gives the
-                            // tested distance (64 threads per k, one word each; a mismatch tags
-                            // sh[48 + k - 2] with the round); the test below then verifies it.
-                            {
-                                const uint32_t ki = (uint32_t)t >> 6, k = ki + 2, bq = r0 + 4 * ((uint32_t)t & 63);
-                                if (ki < 15 && dl % k == 0 && bq + 4 <= nb) {
-                                    const uint32_t dk = dl / k, ia = (bq - dk) >> 2, sk = (bq - dk) & 3;
-                                    if (data32[bq >> 2] != __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sk))
-                                        atomicMax(&S.sh[48 + ki], rr + 1);
-                                }
-                            }
-                            __syncthreads();  // (uniform: dl and wait are the same in every wave)
-                            uint32_t dsel = dl;
-#pragma unroll
-                            for (uint32_t k = 2; k <= 16; k++)
-                                dsel = (dl % k == 0 && S.sh[48 + k - 2] != rr + 1) ? dl / k : dsel;
-                            dl = __builtin_amdgcn_readfirstlane(dsel);
-                            // words r0 / 4 + t + 1024 j (neighbouring lanes, neighbouring words:
-                            // no bank conflicts) against the words dl bytes before them
-                            skip_d = dl;
-                            const uint32_t sa = (r0 - dl) & 3;  // (r0 is a multiple of 4)
-                            uint32_t mm = 0xFFFFFFFFu;
-#pragma unroll
-                            for (int j = 7; j >= 0; j--) {
-                                const uint32_t bq = r0 + 4 * ((uint32_t)t + DF_NT * j);
-                                if (bq < nb) {
-                                    const uint32_t ia = (bq - dl) >> 2;
-                                    const uint32_t df = data32[bq >> 2] ^
-                                                        __builtin_amdgcn_alignbyte(data32[ia + 1], data32[ia], sa);
-                                    mm = df ? bq + ((uint32_t)__builtin_ctz(df) >> 3) : mm;
-                                }
-                            }
-                            if (mm != 0xFFFFFFFFu) atomicMax(&S.sh[46], ((rr + 1) << 16) | (0xFFFFu - mm));
+                            run_test(dl);
                         }
                     }
                     __syncthreads();
-                    if (SKIP && tested) {
-                        // positions p < m - 3 have their key verified at skip_d (m: first mismatch)
-                        const uint32_t mt = __builtin_amdgcn_readfirstlane(S.sh[46]);
-                        const uint32_t m = (mt >> 16) == rr + 1 ? 0xFFFFu - (mt & 0xFFFFu) : 0xFFFFFFFFu;
-                        skip_end = m >= nb ? nb : (m >= 3 ? m - 3 : 0u);
-                        if (TERMRUN && skip_end >= nb) {  // a terminal run: the rounds end here
-                            if (t == 0) {                  // (see run_lo)
-                                S.sh[45] = r0;
-                                S.sh[47] = skip_d;
-                            }
-                            skipped = true;
-                            return;
-                        }
-                        if (r0 + RP <= skip_end || (!TERMRUN && skip_end >= nb)) {  // this round is inside the run
+                    if (!TESTFIRST && SKIP && tested) {
+                        skip_end = tested_end();
+                        if (r0 + RP <= skip_end || skip_end >= nb) {  // this round is inside the run
                             if (act && (FULL || p0 < nb))
                                 cand32[p0 >> 1] = (ok0 ? skip_d : 0u) | ((ok1 ? skip_d : 0u) << 16);
                             cur = RoundState{NOH, NOH, p0, 0, 0, false, false};
@@ -818,7 +868,10 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             if (skipped) __syncthreads();  // skipped rounds end without a barrier
             if (TERMRUN && skipped) {
                 run_lo = __builtin_amdgcn_readfirstlane(S.sh[45]);
-                run_d = __builtin_amdgcn_readfirstlane(S.sh[47]);
+                run_d = __builtin_amdgcn_readfirstlane(S.sh[47]) & 0xFFFFu;
+                // (with run_d's range known the compiler makes the candidate fill's pair
+                // run_d | run_d << 16 a multiply by a constant held in a register of its own)
+                if (LITPREFIX) asm volatile("" : "+s"(run_d));
             }
             DMX_PHASE(A.dbg, seg, 14);
         }
@@ -884,12 +937,18 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         }
         if (level >= 2) {
             // match bitmap from the candidates: bit p = "a candidate starts at p"
+            [[maybe_unused]] uint32_t mfirst = RUN_NONE;  // the first bit at or above D of the thread's word
             for (uint32_t w = t; w < NMAP; w += DF_NT) {
                 if (TERMRUN && 32 * w >= run_lo) {
                     // the terminal run (run_lo is a multiple of 32): every position with four
                     // bytes left has the candidate run_d
                     const uint32_t b0 = 32 * w;
-                    S.mmap[w] = nb >= b0 + 35 ? 0xFFFFFFFFu : (nb > b0 + 3 ? (1u << (nb - 3 - b0)) - 1u : 0u);
+                    const uint32_t v = nb >= b0 + 35 ? 0xFFFFFFFFu : (nb > b0 + 3 ? (1u << (nb - 3 - b0)) - 1u : 0u);
+                    S.mmap[w] = v;
+                    if (LITPREFIX) {
+                        const uint32_t x = b0 + 32 <= D ? 0u : (b0 < D ? v & (0xFFFFFFFFu << (D & 31)) : v);
+                        mfirst = x ? b0 + (uint32_t)__builtin_ctz(x) : RUN_NONE;
+                    }
                     continue;
                 }
                 const uint4* c4 = reinterpret_cast<const uint4*>(S.cand + 32 * w);
@@ -905,7 +964,22 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                     }
                 }
                 const uint32_t b0 = 32 * w;  // positions past the segment end hold stale entries
-                S.mmap[w] = b0 + 32 <= nb ? m : (nb > b0 ? m & ((1u << (nb - b0)) - 1u) : 0u);
+                const uint32_t v = b0 + 32 <= nb ? m : (nb > b0 ? m & ((1u << (nb - b0)) - 1u) : 0u);
+                S.mmap[w] = v;
+                if (LITPREFIX) {
+                    const uint32_t x = b0 + 32 <= D ? 0u : (b0 < D ? v & (0xFFFFFFFFu << (D & 31)) : v);
+                    mfirst = x ? b0 + (uint32_t)__builtin_ctz(x) : RUN_NONE;
+                }
+            }
+            if (LITPREFIX && run_lo != RUN_NONE) {
+                // fm, the first match bit at or above D (a run segment): the words ascend with the
+                // lanes (one word per thread), so a wave's first lane with a bit holds the wave's
+                // minimum: one atomicMin per wave, ordered by the barrier below.  fm shares sh[47]
+                // with run_d (fm << 16 | run_d: the minimum of the words is the minimum of fm); a
+                // slot of its own cost a register for its address, which the kernel does not have
+                const uint64_t has = __ballot(mfirst != RUN_NONE);
+                if (has && ((uint32_t)t & 63u) == (uint32_t)__builtin_ctzll(has))
+                    atomicMin(&S.sh[47], (mfirst << 16) | run_d);
             }
             if (TERMRUN && run_lo != RUN_NONE) {
                 // the terminal run's candidates (nb > run_lo >= 2 * DF_NT): eight positions per
@@ -930,8 +1004,21 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             if (TERMRUN && run_lo != RUN_NONE) {
                 constexpr uint32_t RP = 2 * DF_NT;
                 const uint32_t et = __builtin_amdgcn_readfirstlane(S.sh[43]);
+                // (read with sh[43]: one wait for both)
+                [[maybe_unused]] const uint32_t fw = LITPREFIX ? (uint32_t)__builtin_amdgcn_readfirstlane(S.sh[47]) : 0u;
                 run_e = (et >> 16) == run_lo / RP + 1 ? et & 0xFFFFu : max(run_lo - RP, (run_d + 3) & ~3u);
                 run_rcp = __builtin_amdgcn_rcpf((float)run_d);
+                if (LITPREFIX) {
+                    // Literal prefix: the positions of [D, fm) have no match bit, so each is a
+                    // literal token whatever precedes it.  Their token bits are set here by bitmap
+                    // word (the walk ORs into the same words), and the walk starts at fm.  No bit
+                    // at all: 0xFFFF, so fm = nb.
+                    run_fm = min(fw >> 16, nb);
+                    const uint32_t a = max(D, 32u * (uint32_t)t), b = min(run_fm, 32u * (uint32_t)t + 32u);
+                    if (a < b)
+                        atomicOr(&S.tokmap[t], (b - 32u * (uint32_t)t >= 32 ? 0xFFFFFFFFu : ((1u << (b & 31)) - 1u)) &
+                                                   (0xFFFFFFFFu << (a & 31)));
+                }
             }
         }
         DMX_PHASE(A.dbg, seg, 2);
@@ -977,7 +1064,13 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             auto full_len = [&](uint32_t q) -> uint32_t {  // < 3 only on a fingerprint collision
                 return len_at(q, S.cand[q], min(258u, hi - q));
             };
-            uint32_t p = lo, w = lo >> 5, mw = S.mmap[w], tok = 0, lastp = lo;  // lastp: last token
+            uint32_t p = lo;
+            // (see the literal prefix above) the walk starts at the first match bit or behind the
+            // chunk: a chunk below the bit is literals, the last of them its last token, and in
+            // the chunk that holds the bit the walk's first step is the match there
+            if (RUNW && LITPREFIX) p = min(max(lo, run_fm), hi);
+            uint32_t lastp = RUNW && LITPREFIX ? min(p, hi - 1) : lo;  // lastp: last token
+            uint32_t w = lastp >> 5, mw = S.mmap[w], tok = 0;
             auto mbit = [&](uint32_t q) -> bool {
                 return (S.mmap[q >> 5] >> (q & 31)) & 1u;
             };
