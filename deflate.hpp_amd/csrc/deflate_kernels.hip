@@ -346,8 +346,8 @@ struct DfSmem : DfBufs<SEG, df_early(SEG)> {
     uint32_t tokmap[SEG / 32];  // token-start bitmap (parse walk; chunks share boundary words)
     uint16_t lasttok[NWALK + 1];  // last token start of each parse chunk
     uint32_t scan[4 * DF_NT / 64];
-    uint32_t sh[64];  // 43: backward mismatch tag, 44: run candidate, 45 / 47: terminal run (47:
-                      // its distance | first match bit << 16), 46: mismatch tag, 48..62:
+    uint32_t sh[64];  // 43: backward mismatch tag, 44: run candidate, 47: a run segment's first
+                      // match bit << 16 | the run's distance, 46: mismatch tag, 48..62:
                       // divisor-period tags
 };
 static_assert(sizeof(DfSmem<32768>) <= 160 * 1024, "the front kernel's LDS fits a CU's 160 KiB");
@@ -568,7 +568,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         for (uint32_t i = nb + t; i < ((nb + 3) & ~3u) + 32; i += DF_NT) dbytes[i] = 0;
         if (t < NMAP) S.tokmap[t] = 0;
         if (t == 0) S.sh[46] = 0;  // the match rounds' mismatch tag (run continuation)
-        if (TERMRUN && t == 1) S.sh[45] = RUN_NONE;  // its terminal run's first position
+        if (TERMRUN && t == 1) S.sh[47] = 0xFFFFFFFFu;  // a run segment's first match bit: none (atomicMin)
         if (TERMRUN && t == 2) S.sh[43] = 0;  // the run's last mismatch in the round before it
         if (t >= 48 && t < 63) S.sh[t] = 0;  // its divisor-period tags
         if (level >= 2 && EARLY) {  // (the previous segment's image, dead since its last barrier)
@@ -586,7 +586,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
         // Terminal run (uniform): the positions [run_lo, nb) repeat at distance run_d up to the
         // segment end, so every one of them with four bytes left has the candidate run_d.  The
         // match rounds end at run_lo (a round's first position).  The round that finds the run
-        // leaves both values in sh[45] and sh[47]: the rounds' loop carries no state for them.
+        // sets both as it leaves: they are uniform there, and scalar from here on.
         [[maybe_unused]] uint32_t run_lo = RUN_NONE, run_d = 0;
         // The run's proven start (uniform), run_e <= run_lo: data[q] == data[q - run_d] for every
         // q in [run_e, nb).  Next to the run's candidate fill (not in the round that proves the
@@ -739,12 +739,11 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                             __syncthreads();
                             skip_end = tested_end();
                             if (skip_end >= nb) {  // a terminal run: the rounds end here
-                                if (t == 0) {      // (see run_lo)
-                                    S.sh[45] = r0;
-                                    // (upper half: the first match bit, none yet -- see the bitmap)
-                                    S.sh[47] = skip_d | (LITPREFIX ? 0xFFFF0000u : 0u);
-                                }
-                                skipped = true;
+                                // (see run_lo: r0, skip_d and skip_end are the same in every wave,
+                                // read behind the barrier above; no barrier and no LDS word hands
+                                // them on)
+                                run_lo = r0;
+                                run_d = skip_d;
                                 return;
                             }
                             if (r0 + RP <= skip_end) {  // this round is inside the run
@@ -865,10 +864,24 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 run_rounds(std::integral_constant<uint32_t, DF_L3_RP>{});
             else
                 run_rounds(std::integral_constant<uint32_t, 2 * DF_NT>{});
-            if (skipped) __syncthreads();  // skipped rounds end without a barrier
-            if (TERMRUN && skipped) {
-                run_lo = __builtin_amdgcn_readfirstlane(S.sh[45]);
-                run_d = __builtin_amdgcn_readfirstlane(S.sh[47]) & 0xFFFFu;
+            // Skipped rounds end without a barrier.  The round that proves a terminal run does not:
+            // its last barrier stands behind the test, and after it a wave reads sh[46] and
+            // leaves.  So without a barrier here
+            //  * every LDS access of the bitmap phase below is ordered behind the rounds' last
+            //    write (the test's atomics on sh[46] and sh[48..62], before that barrier), and
+            //    nothing below writes a word the rounds still read (sh[46]: next in the load
+            //    phase of the workgroup's next segment);
+            //  * the candidates the bitmap phase reads lie below run_lo: a round below run_lo
+            //    either ended in a barrier or was skipped inside a run that ended, and then a
+            //    whole round with its barriers followed before this test (round 0 of a `repeat`
+            //    segment, positions [0, 2048), ends in a barrier);
+            //  * the run fill writes only the candidates of positions >= run_lo, which no round
+            //    wrote and none reads;
+            //  * mmap is written below and not read before the bitmap phase's barrier.
+            if (skipped && !(TERMRUN && run_lo != RUN_NONE)) __syncthreads();
+            if (TERMRUN && run_lo != RUN_NONE) {
+                run_lo = __builtin_amdgcn_readfirstlane(run_lo);
+                run_d = __builtin_amdgcn_readfirstlane(run_d);
                 // (with run_d's range known the compiler makes the candidate fill's pair
                 // run_d | run_d << 16 a multiply by a constant held in a register of its own)
                 if (LITPREFIX) asm volatile("" : "+s"(run_d));
@@ -1305,7 +1318,15 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
             // mt: the tokens with a candidate, the matches; lt: the literals.  A literal is one
             // position long, so the literals between two matches are adjacent bits of lt, and
             // such a run's words start at its first bit and every third one after it (ws).
-            const uint32_t m = S.tokmap[t];
+            // The literal prefix [D, run_fm) (see the bitmap phase) is not worded per thread: its
+            // bytes are contiguous in the image, so its word k is the bytes D + 3k .. D + 3k + 2,
+            // W0 = ceil(P / 3) words that any thread can make (below, before the per-thread loop).
+            // Thread t drops the bits below run_fm from its word; the token at run_fm (a match,
+            // or a literal where the match came out shorter than three bytes) starts a word of
+            // its thread as before.
+            const uint32_t P = run_fm - D, W0 = (P + 2) / 3;
+            const int32_t fr = (int32_t)run_fm - 32 * t;  // run_fm in the thread's word: bit fr
+            const uint32_t m = fr >= 32 ? 0u : S.tokmap[t] & (fr > 0 ? 0xFFFFFFFFu << fr : 0xFFFFFFFFu);
             const uint4* const c4 = reinterpret_cast<const uint4*>(S.cand + 32 * t);
             uint32_t nz = 0;
 #pragma unroll
@@ -1339,10 +1360,29 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                 tot += x;
             }
             DMX_PHASE(A.dbg, seg, 15);
-            if ((tot >> 16) == nb - D) {  // (the emission kernel's rule; a run segment has a match)
+            // (the scan counts what the threads word; the prefix adds P tokens and W0 words)
+            if ((tot >> 16) + P == nb - D) {  // (the emission kernel's rule; a run segment has a match)
                 if (t == 0) A.ntok[seg] = EM_ALL_LITERALS;
             } else {
-                uint32_t* dst = A.tok + seg * (uint64_t)A.tok_stride + (ex & 0xFFFFu);
+                uint32_t* dst = A.tok + seg * (uint64_t)A.tok_stride;
+                // The prefix words, word k by thread k mod DF_NT (W0 exceeds DF_NT behind a long
+                // incompressible head): one unaligned read of the image (the bytes past nb are
+                // zero padding) and one store, neighbouring threads on neighbouring words.  Issued
+                // before the loop below, whose LDS reads overlap these stores.
+                // Capacity: the n positions of run_fm's bitmap word from run_fm on make at most
+                // n / 2 + 1 words, as any n positions do (above), and the P before them
+                // ceil(P / 3) <= P / 2 (P >= 4) or one (P <= 3, where n >= 29 and 1 + n / 2 + 1
+                // <= 17): the bitmap words up to run_fm's stay within 17 words each in the sum,
+                // the later ones each, the segment within 17408.  Against the grouping by bitmap
+                // word the prefix never takes more words (ceil(P / 3) <= the sum of ceil(P_t / 3)
+                // over the bitmap words).  Only a literal AT run_fm (a match bit clipped below
+                // three bytes at its chunk's end, or a fingerprint collision) that shared a word
+                // with the prefix's last literals now starts one of its own: one word more.
+                for (uint32_t k = t; k < W0; k += DF_NT) {
+                    const uint32_t c = min(3u, P - 3 * k);
+                    dst[k] = (lds_rd32u(data32, D + 3 * k) & (0xFFFFFFu >> (24 - 8 * c))) | (c << 24);
+                }
+                dst += W0 + (ex & 0xFFFFu);
                 // Four words per step, their LDS reads issued together: two 32-bit words from
                 // the candidates (a match: its distance and, one entry on, its length) or from
                 // the image (one to three literals: the adjacent bits of lt), as word offsets
@@ -1374,7 +1414,7 @@ __device__ __forceinline__ void deflate_segment(const DeflateArgs& A, DfSmem<SEG
                         }
                     }
                 }
-                if (t == 0) A.ntok[seg] = tot & 0xFFFFu;
+                if (t == 0) A.ntok[seg] = (tot & 0xFFFFu) + W0;
             }
         } else {
             // ---- token ranges (TokRange): per-word token counts, block scan into the match
