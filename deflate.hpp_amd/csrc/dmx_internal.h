@@ -12,6 +12,7 @@
 #include "seek_plan.h"        // SeekSpan, SeekSpanHead, SeekSlot and the seek planners (plain C++, shared with the CPU test)
 #include "gzip_members.h"     // GzmCand, GzmRec and the member walk (plain C++, shared with the CPU test)
 #include "zip_dir.h"          // ZipHead and the ZIP directory's steps (plain C++, shared with the CPU test)
+#include "zip_write.h"        // ZipwSrc, ZipwHead and the ZIP writer's records and steps (plain C++, shared with the CPU test)
 
 namespace dmx {
 
@@ -434,5 +435,24 @@ hipError_t launch_zip_copy(const InflateBatchDesc* desc, const uint32_t* kind, u
 // res[k].status of the decoded and the copied entries by zip_verdict (side[k].ck: the output's CRC-32)
 hipError_t launch_zip_verdict(const ::dmx_zip_entry* ents, const uint32_t* kind, const FrameHead* side, uint64_t count,
                               bool verify, ::dmx_batch_result* res, hipStream_t st);
+
+// ZIP archives written in device memory (zip_write.hip; the records and the steps: zip_write.h).
+// The layout of `count` > 0 entries: src[k] and desc[k] = {plain input, n, payload source, -} as
+// uploaded, res = the batch deflate's results over the method 8 entries.  csize / loff: count
+// entries, lo / hi / cbytes: count words, off_lo / off_hi / coff: scan_words(count) entries each,
+// totals: 3 words (the local records' low and high halves, the directory), *key preset to all ones.
+hipError_t launch_zipw_layout(const ZipwSrc* src, const InflateBatchDesc* desc, const ::dmx_batch_result* res,
+                              uint64_t count, bool force64, uint64_t* csize, uint32_t* lo, uint32_t* hi,
+                              uint64_t* off_lo, uint64_t* off_hi, uint64_t* loff, uint32_t* cbytes, uint64_t* coff,
+                              uint64_t* totals, unsigned long long* key, hipStream_t st);
+// Behind the layout and launch_checksum_batch (side[k].ck = the CRC-32 of plain input k): the
+// payloads, the records, the comment, *head and the written table rows[0, count).  first: the
+// exclusive prefix sum of zipw_chunk_bound over the entries' payload bounds, nchunks = first[count]
+// < 2^31 - 1.  Nothing is written to out unless every entry is DMX_OK and the archive fits cap.
+hipError_t launch_zipw_pack(const ZipwSrc* src, const InflateBatchDesc* desc, const FrameHead* side,
+                            const uint8_t* names, const uint8_t* comment, uint32_t comment_len, const uint64_t* first,
+                            uint64_t count, uint64_t nchunks, const uint64_t* csize, const uint64_t* loff,
+                            const uint64_t* coff, const uint64_t* totals, const unsigned long long* key, bool force64,
+                            uint8_t* out, uint64_t cap, ZipwHead* head, ::dmx_zip_entry* rows, hipStream_t st);
 
 }  // namespace dmx

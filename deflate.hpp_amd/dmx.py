@@ -32,6 +32,7 @@ DMX_FRAME_ZLIB = 1
 DMX_FRAME_GZIP = 2
 DMX_FRAME_BGZF = 3
 FRAME = {"zlib": DMX_FRAME_ZLIB, "gzip": DMX_FRAME_GZIP, "bgzf": DMX_FRAME_BGZF}
+DMX_ZIP_FORCE64 = 1
 DMX_SEEK_WINDOW = 32768
 DMX_SEEK_NOWINDOW = 1  # dmx_seek_entry.flags: nothing before the entry is referenced
 BATCH_PATH = 6  # dmx_batch_result.path of a stream the batch decoder took
@@ -57,6 +58,7 @@ EXPORTS = [
     "dmx_seek_windows_bound", "dmx_inflate_index_device", "dmx_inflate_range_device",
     "dmx_inflate_gzip_members_device", "dmx_inflate_gzip_members",
     "dmx_zip_index_device", "dmx_zip_extract_device", "dmx_inflate_zip_device", "dmx_zip_index", "dmx_inflate_zip",
+    "dmx_zip_bound", "dmx_zip_write_device", "dmx_zip_write",
 ]
 
 
@@ -95,6 +97,14 @@ class ZipEntry(ctypes.Structure):
                 ("dostime", ctypes.c_uint32), ("name_len", ctypes.c_uint16), ("method", ctypes.c_uint16),
                 ("gpflags", ctypes.c_uint16), ("reserved", ctypes.c_uint16), ("status", ctypes.c_int32),
                 ("path", ctypes.c_uint32)]
+
+
+class ZipSource(ctypes.Structure):
+    """dmx_zip_source: one entry to write -- its plain bytes (a device pointer for the device form), its
+    name (host bytes), the method (0 stored, 8 deflated) and the DOS time (0: 1980-01-01), 40 bytes."""
+    _fields_ = [("data", ctypes.c_void_p), ("n", ctypes.c_uint64), ("name", ctypes.c_char_p),
+                ("name_len", ctypes.c_uint32), ("method", ctypes.c_uint16), ("reserved", ctypes.c_uint16),
+                ("dostime", ctypes.c_uint32)]
 
 
 class SeekEntry(ctypes.Structure):
@@ -200,6 +210,11 @@ def lib():
     L.dmx_inflate_zip_device.argtypes = [vp, vp, sz, u32, vp, sz, zep, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
     L.dmx_zip_index.argtypes = [vp, vp, sz, zep, sz, ctypes.POINTER(sz), ctypes.POINTER(u64)]
     L.dmx_inflate_zip.argtypes = [vp, vp, sz, u32, vp, sz, zep, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    zsp = ctypes.POINTER(ZipSource)
+    L.dmx_zip_bound.argtypes = [zsp, sz, sz, u32]
+    L.dmx_zip_bound.restype = sz
+    L.dmx_zip_write_device.argtypes = [vp, zsp, sz, ctypes.c_int, u32, vp, sz, vp, sz, zep, ctypes.POINTER(sz), vp]
+    L.dmx_zip_write.argtypes = [vp, zsp, sz, ctypes.c_int, u32, vp, sz, vp, sz, zep, ctypes.POINTER(sz)]
     sep = ctypes.POINTER(SeekEntry)
     L.dmx_seek_windows_bound.argtypes = [sz, sz]
     L.dmx_seek_windows_bound.restype = sz
@@ -224,6 +239,29 @@ def _check(rc, what):
 
 def deflate_bound(n):
     return lib().dmx_deflate_bound(n)
+
+
+def zip_sources(ptrs, sizes, names, methods=None, dostimes=None):
+    """The ZipSource array of a write call: names are bytes (str: encoded as UTF-8), methods default
+    to 8 (deflated), dostimes to 0 (1980-01-01 00:00:00).  The array keeps the names alive."""
+    k = len(ptrs)
+    names = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in names]
+    arr = (ZipSource * max(k, 1))()
+    for i in range(k):
+        arr[i].data = ptrs[i] or None
+        arr[i].n = sizes[i]
+        arr[i].name = names[i]
+        arr[i].name_len = len(names[i])
+        arr[i].method = 8 if methods is None else methods[i]
+        arr[i].dostime = 0 if dostimes is None else dostimes[i]
+    arr._names = names
+    return arr
+
+
+def zip_bound(sizes, names, methods=None, comment=b"", force64=False):
+    """dmx_zip_bound: no archive written from these entries is longer."""
+    src = zip_sources([0] * len(sizes), sizes, names, methods)
+    return lib().dmx_zip_bound(src, len(sizes), len(comment), DMX_ZIP_FORCE64 if force64 else 0)
 
 
 def seek_windows_bound(cap, spacing=262144):
@@ -815,6 +853,43 @@ class Context:
             got[decoded[k]] = host[at:at + entries[k].usize]
             at += entries[k].usize
         return got
+
+    def zip_write_device(self, ptrs, sizes, names, d_out, cap, level=2, methods=None, dostimes=None, comment=b"",
+                         force64=False, stream=None):
+        """A ZIP archive of the buffers at device pointers ptrs, written at device pointer d_out
+        (dmx_zip_write_device) -> (bytes, entries): the archive's size and the ZipEntry rows
+        zip_index_device reads back from it.  names: bytes or str (UTF-8); methods: 8 (deflated, the
+        default) or 0 (stored) per entry.  A DMX_ERR_CAPACITY error carries the size that was needed
+        as .needed; zip_bound(sizes, names, ...) is always enough."""
+        k = len(ptrs)
+        src = zip_sources(ptrs, sizes, names, methods, dostimes)
+        comment = bytes(comment)
+        ent = (ZipEntry * max(k, 1))()
+        out_len = ctypes.c_size_t()
+        rc = lib().dmx_zip_write_device(self.h, src, k, level, DMX_ZIP_FORCE64 if force64 else 0, comment,
+                                        len(comment), ctypes.c_void_p(d_out), cap, ent, ctypes.byref(out_len),
+                                        ctypes.c_void_p(stream) if stream else None)
+        self._check_needed(rc, "zip_write_device", out_len.value)
+        return out_len.value, (ZipEntry * k).from_buffer(ent)
+
+    def zip(self, members, level=2, stored=(), comment=b"", force64=False):
+        """The inverse of unzip: members, a dict or a list of (name, bytes), -> the archive's bytes
+        (dmx_zip_write).  Entries are deflated at `level` but for the names in `stored`."""
+        items = [(k, bytes(v)) for k, v in (members.items() if isinstance(members, dict) else members)]
+        bufs = [ctypes.create_string_buffer(v, max(1, len(v))) for _, v in items]
+        sizes = [len(v) for _, v in items]
+        names = [k for k, _ in items]
+        methods = [0 if k in stored else 8 for k in names]
+        src = zip_sources([ctypes.addressof(b) for b in bufs], sizes, names, methods)
+        comment = bytes(comment)
+        fl = DMX_ZIP_FORCE64 if force64 else 0
+        cap = lib().dmx_zip_bound(src, len(items), len(comment), fl)
+        out = ctypes.create_string_buffer(max(1, cap))
+        out_len = ctypes.c_size_t()
+        rc = lib().dmx_zip_write(self.h, src, len(items), level, fl, comment, len(comment), out, cap, None,
+                                 ctypes.byref(out_len))
+        self._check_needed(rc, "zip_write", out_len.value)
+        return out.raw[:out_len.value]
 
     # ---- seek index and ranged reads for unblocked streams ---------------------------------
     def inflate_index_device(self, d_in, n, d_out, cap, spacing=262144, stream=None):

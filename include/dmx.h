@@ -658,9 +658,9 @@ int dmx_inflate_gzip_members(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t
  * there) and return after their last host synchronisation.  A context with n_gpus > 1 runs them on
  * its first device.
  *
- * Not covered: writing archives, encryption, methods other than 0 and 8, multi-disk archives, a
- * ZIP64 end record with extensible data (it is looked for directly in front of its locator),
- * comparing local with central names, graph capture. */
+ * Not covered: encryption, methods other than 0 and 8, multi-disk archives, a ZIP64 end record
+ * with extensible data (it is looked for directly in front of its locator), comparing local with
+ * central names, graph capture.  (Writing archives: the dmx_zip_write calls below.) */
 typedef struct dmx_zip_entry {      /* 64 bytes */
     uint64_t name_off;   /* the name's first byte in the archive (inside the central directory) */
     uint64_t data_off;   /* the entry's first data byte */
@@ -683,6 +683,71 @@ int dmx_zip_index(dmx_ctx* ctx, const uint8_t* in, size_t n, dmx_zip_entry* entr
                   size_t* count, uint64_t* plain_bytes);
 int dmx_inflate_zip(dmx_ctx* ctx, const uint8_t* in, size_t n, uint32_t flags, uint8_t* out, size_t cap,
                     dmx_zip_entry* entries, size_t entry_cap, size_t* count, size_t* out_len);
+
+/* ---- ZIP archives: writing (not in the reference) ------------------------------------------------
+ * The inverse of the calls above for buffers that already sit in device memory: .npz files,
+ * checkpoints, zipped dataset shards.  Entry k is written with method 8 (its payload is exactly the
+ * raw stream dmx_deflate_batch_device writes for that buffer at that level) or method 0 (stored).
+ * Sizes and CRC-32 are known before a header is written, so flag bit 3 is never set and there is no
+ * data descriptor; flag bit 11 (UTF-8) is set iff the name holds a byte above 127.  The layout, in
+ * archive order: per entry the local header (30 bytes, the name, and a ZIP64 extra 0x0001 of 16
+ * bytes {usize, csize} when DMX_ZIP_FORCE64 is given or either size is >= 0xFFFFFFFF: both 32-bit
+ * fields then read 0xFFFFFFFF and "version needed" is 45, else 20) and the payload; the central
+ * directory (46 bytes and the name per entry, the extra 0x0001 with usize and csize under the same
+ * rule, then the local header's offset when DMX_ZIP_FORCE64 is given or it is >= 0xFFFFFFFF;
+ * external attributes 0x10 for a name that ends in '/', else 0); the ZIP64 end record (56 bytes)
+ * and its locator (20 bytes) when DMX_ZIP_FORCE64 is given, or there are 65535 entries or more, or
+ * the directory's size or offset is >= 0xFFFFFFFF -- the classic record then reads 0xFFFF, 0xFFFF,
+ * 0xFFFFFFFF and 0xFFFFFFFF; the 22-byte end record and the archive comment.  The archive is a
+ * pure function of the arguments: dostime 0 is written as 1980-01-01 00:00:00 (0x00210000).
+ * Python's zipfile reads it (testzip() is None); without entries and without a comment it is the
+ * 22 bytes zipfile writes.
+ *
+ * dmx_zip_bound: the archive's size with every deflated payload at dmx_deflate_bound of its n (no
+ *   device work, no checks); an archive of these sources is never longer.
+ * dmx_zip_write_device: src is a HOST array; data are DEVICE pointers of any alignment, d_out a
+ *   DEVICE pointer of any alignment.  One upload carries the sources, the names and the comment;
+ *   one batch deflate compresses the method 8 entries into context scratch; one checksum launch
+ *   gives every plain input's CRC-32; the layout is two prefix sums on the device; one launch then
+ *   moves every payload byte once, from its scratch slot or the caller's plain input to its final
+ *   place -- in chunks of 64 KiB, so one large entry spreads over the device -- and writes the
+ *   records.  *out_len = the archive's bytes.  entries (HOST memory, `count` rows, may be NULL)
+ *   receive the table dmx_zip_index_device reads back from the written archive (status 0, path 0).
+ *     DMX_ERR_ARG, before any device work and with nothing written: a null context, src == NULL
+ *       with count > 0, out_len == NULL, d_out == NULL with cap > 0, data == NULL with n > 0, a
+ *       method other than 0 and 8, name == NULL, name_len 0 or above 65535, a comment above 65535
+ *       bytes or NULL with comment_len > 0, flags other than DMX_ZIP_FORCE64, 2^31 entries or
+ *       more, a context whose segment_bytes is 65536 (as every batch deflate call).
+ *     DMX_ERR_CAPACITY: the archive does not fit cap; *out_len = the size needed, nothing is
+ *       written to d_out.  A deflate that fails returns its status, nothing is written either.
+ *   Host synchronisations: 2 -- the batch deflate's read-back (none when no entry is method 8) and
+ *   the read-back of the status, the size and the table.  count == 0: 1.
+ * dmx_zip_write: the same on host buffers (data: HOST pointers): the plain inputs are staged with
+ *   one copy to the device, the device form runs there, the archive is copied back with one copy.
+ *
+ * The calls take the context mutex, are ordered against the context's other deflate / inflate work
+ * like dmx_deflate_bgzf_device, run on `stream` (NULL: the context's stream; the host form always
+ * there) and return after their last host synchronisation.
+ *
+ * Not covered: falling back to method 0 when deflate does not shrink an entry, entry comments and
+ * extras other than 0x0001, encryption, appending to an existing archive, graph capture. */
+typedef struct dmx_zip_source {   /* one entry to write; HOST array; 40 bytes */
+    const void* data;     /* DEVICE pointer (device form) / host pointer (host form); may be NULL when n == 0 */
+    uint64_t    n;
+    const char* name;     /* HOST bytes, not NUL-terminated */
+    uint32_t    name_len; /* 1..65535, above that DMX_ERR_ARG */
+    uint16_t    method;   /* 0 stored, 8 deflated */
+    uint16_t    reserved; /* 0 */
+    uint32_t    dostime;  /* time | date << 16; 0 means 1980-01-01 00:00:00 (0x00210000) */
+} dmx_zip_source;
+#define DMX_ZIP_FORCE64 1u  /* ZIP64 extras and end records whatever the sizes */
+size_t dmx_zip_bound(const dmx_zip_source* src, size_t count, size_t comment_len, uint32_t flags);
+int dmx_zip_write_device(dmx_ctx* ctx, const dmx_zip_source* src, size_t count, int level, uint32_t flags,
+                         const void* comment, size_t comment_len, void* d_out, size_t cap, dmx_zip_entry* entries,
+                         size_t* out_len, void* stream);
+int dmx_zip_write(dmx_ctx* ctx, const dmx_zip_source* src, size_t count, int level, uint32_t flags,
+                  const void* comment, size_t comment_len, uint8_t* out, size_t cap, dmx_zip_entry* entries,
+                  size_t* out_len);
 
 /* ---- seek index and ranged reads for unblocked streams (zran's idea; not in the reference) -----
  * BGZF is blocked for random access; an ordinary zlib / gzip / pigz stream and libdmx's own output
